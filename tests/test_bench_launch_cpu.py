@@ -39,3 +39,12 @@ def test_one_rank_dying_at_start_ends_the_job_within_seconds():
     assert "injected failure of this rank" in out.stderr
     assert "---- rank 0 (exit code -15)" in out.stderr or "---- rank 0 (exit code -9)" in out.stderr, out.stderr[-2000:]
     assert took < 60, took      # (import torch x 2 dominates; the store timeout would be >= 600 s)
+
+
+def test_steps_below_one_is_refused():
+    """--steps sets the number of timed steps, and ms_per_step divides by it: zero is an argument error, before any GPU work."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0"],
+                         cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 2 and "--steps must be at least 1" in out.stderr, out.stderr[-2000:]
+    assert not [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -218,14 +218,38 @@ def test_cfg5_training_step_matches_the_cpu_checker():
 @pytest.mark.parametrize("cfg", ["cfg3", "cfg4", "cfg5"])
 def test_bench_runs_every_config(cfg):
     """bench.py --config cfgN end to end (2 scenes per GPU to keep the test short; the default is the config's own
-    per-GPU batch)."""
+    per-GPU batch; --full: the roofline, drop-in and inference records run as well)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--batch", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert rec["value"] > 0 and rec["final_loss"] == rec["final_loss"] and cfg in rec["config"]["workload"]
     assert rec["config"]["hip_graph"] is True, "the hipGraph capture must work for every config"
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain bench.py run: the headline line only (nothing that --full measures), --steps timed steps, and with
+    --dump-outputs the last timed step's loss terms, parameters, gradient and BatchNorm statistics as float .npy files within
+    64 MB (the default model's parameters and gradient are a seeded sample of their elements)."""
+    out_dir = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "2", "--steps", "3", "--warmup", "2",
+           "--dump-outputs", str(out_dir)]
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["warmup"] == 2 and rec["unit"] == "scenes/s" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "f32" and rec["metric"].startswith("scenes/sec")
+    assert abs(rec["value"] - 2 / (rec["ms_per_step"] * 1e-3)) < 1e-6 * rec["value"]
+    assert not {"roofline", "roofline_more", "ops", "drop_in", "eval", "configs", "cpu_baseline"} & set(rec)
+    files = {f.name: np.load(f) for f in out_dir.iterdir()}
+    assert {"loss.npy", "cap_loss.npy", "parameters.npy", "gradients.npy", "bn_running_stats.npy"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert sum(f.stat().st_size for f in out_dir.iterdir()) <= 64 * 10 ** 6
+    assert float(files["loss.npy"]) == rec["final_loss"]
+    assert files["parameters.npy"].shape == files["gradients.npy"].shape and np.abs(files["gradients.npy"]).max() > 0
 
 
 def test_cfg5_wide_relation_head_at_full_size_on_sampled_pair_rows():
