@@ -892,6 +892,47 @@ int spacap_stream_signal(int64_t *flag, const int64_t *value, spacap_stream_t st
 /* Lab only (tools/lab/step_stamps.py): writes the device's 100 MHz wall clock into *slot when the stream reaches it. */
 int spacap_lab_stamp(uint64_t *slot, spacap_stream_t stream);
 
+/* ---- evaluation post-processing (replaces lib/ap_helper.py:45-160 parse_predictions' host work and the IoU of
+ * lib/eval_helper.py:146-177; csrc/postprocess.hip) ---------------------------------------------------------------------- */
+
+/* Points-in-box counts, step 1 of 2.  point_clouds f32 [B,N,C] (xyz = the first 3 of C channels), bbox_corner f64
+ * [B,K,8,3] -> per-chunk partial counts in `workspace` (i32 [B, ceil(N/1024), K], every element written; no atomics).
+ * The reference tests each point against a scipy Delaunay hull of the 8 corners (data/scannet/model_util_scannet.py:13-22);
+ * the boxes this model decodes are axis-aligned (heading 0, NUM_HEADING_BIN = 1), so the hull is the corners' axis-aligned
+ * bounding box and the test here is the closed box lo <= p <= hi, exact in f32 (each f64 bound rounded inwards to a float).
+ * 1 <= K <= 512, N >= 1, C >= 3; size the workspace with spacap_points_in_box_workspace_bytes. */
+size_t spacap_points_in_box_workspace_bytes(int B, int N, int K);
+int spacap_points_in_box_f32(const float *point_clouds, int B, int N, int C, const double *bbox_corner, int K, void *workspace,
+                             size_t workspace_bytes, spacap_stream_t stream);
+
+/* flags of spacap_detection_nms_f32 (POST_DICT of scripts/eval.py:201-210) */
+#define SPACAP_PP_REMOVE_EMPTY 1 /* "remove_empty_box": boxes with fewer than min_points points take no part   */
+#define SPACAP_PP_CLS_NMS 2      /* "cls_nms": nms_3d_faster_samecls (utils/nms.py:110-150), else nms_3d_faster */
+#define SPACAP_PP_OLD_TYPE 4     /* "use_old_type_nms": overlap = inter / area of the box being suppressed      */
+#define SPACAP_PP_GT_F32 8       /* gt_corner holds widened f32 labels: their volume is an f32 product, as in torch */
+
+/* Step 2 of 2, one workgroup per scene: sums the count slab of spacap_points_in_box_f32 (same B, N, K) and runs
+ * lib/ap_helper.py:77-148 with use_3d_nms.  objectness f32 [B,K,2] logits, sem_cls i64 [B,K], sem_cls_scores f32 [B,K,NC]
+ * (NULL: no conf; NC <= 128), bbox_corner f64 [B,K,8,3] ->
+ *   obj_prob f32 [B,K]   softmax(objectness)[..., 1] as exp(x - max) / sum (exp correctly rounded; lib/ap_helper.py:37-42),
+ *   count i32 [B,K], nonempty u8 [B,K] = count >= min_points (all ones without SPACAP_PP_REMOVE_EMPTY),
+ *   pred_mask u8 [B,K]   the greedy 3D NMS keep mask over the non-empty boxes (utils/nms.py:77-150): order by obj_prob
+ *                        descending, equal probabilities higher index first (numpy's quicksort leaves ties unspecified);
+ *                        overlaps in f64 as numpy computes them, suppression when overlap > nms_iou.  A scene with no
+ *                        box kept gets an all-zero mask (the reference asserts instead);
+ *   conf f32 [B,K,NC]    softmax(sem_cls_scores) * obj_prob (lib/ap_helper.py:62, 142), when sem_cls_scores is given;
+ *   valid u8 [B,K]       pred_mask && obj_prob > conf_thresh (compared in f32, as numpy 2 compares a float32 scalar);
+ * and, when gt_corner f64 [B,M,8,3] is given (with object_assignment i64 [B,K]): the IoU of each box with its assigned
+ * ground-truth box, box3d_iou_batch_tensor(gt, box) of utils/box_util.py:183-209 in the same operation order ->
+ *   iou f64 [B,K] (NaN where the assignment is outside 0..M-1), good u8 [B,K] = iou > min_iou.
+ * 1 <= K <= 512. */
+int spacap_detection_nms_f32(const float *objectness, const int64_t *sem_cls, const float *sem_cls_scores, int NC,
+                             const double *bbox_corner, const void *workspace, int B, int N, int K, const double *gt_corner,
+                             int M, const int64_t *object_assignment, int flags, int min_points, double nms_iou,
+                             float conf_thresh, double min_iou, float *obj_prob, int32_t *count, uint8_t *nonempty,
+                             uint8_t *pred_mask, float *conf, uint8_t *valid, double *iou, uint8_t *good,
+                             spacap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

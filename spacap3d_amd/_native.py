@@ -86,6 +86,10 @@ SIGNATURES = {
     "spacap_vote_assemble_bwd_f32": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
     "spacap_copy_batched": (_i, [_p, _p, _p, _i, _p]),
     "spacap_lab_stamp": (_i, [_p, _p]),
+    "spacap_points_in_box_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "spacap_points_in_box_f32": (_i, [_p, _i, _i, _i, _p, _i, _p, ctypes.c_size_t, _p]),
+    "spacap_detection_nms_f32": (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _i, _i, ctypes.c_double, _f,
+                                      ctypes.c_double] + [_p] * 8 + [_p]),
     "spacap_stream_delay": (_i, [_i, _p]),
     "spacap_stream_wait_ge": (_i, [_p, _l, _i, _p, _p]),
     "spacap_stream_signal": (_i, [_p, _p, _p]),

@@ -734,10 +734,18 @@ class Evaluator:
     pyramid of the next batch depends on its coordinates only and is computed on a side stream while the current batch
     decodes -- what ``Trainer.prefetch`` does for training steps.  In a single forward the 4.5 ms sampling chain (2 047 + 1 023 +
     511 + 255 dependent rounds on one workgroup per scene) is on the critical path; with a batch in flight it is not.  Values
-    are those of the plain forward (same indices, same kernels)."""
+    are those of the plain forward (same indices, same kernels).
 
-    def __init__(self, model, graph=True):
+    ``postprocess``: a POST_DICT-like mapping (scripts/eval.py:201-210; use_3d_nms only): each call then also runs
+    ``postprocess.detection_postprocess`` on the forward's outputs, on the same stream, and stores its tensors under
+    ``post_obj_prob``, ``post_point_count``, ``post_nonempty_mask``, ``post_pred_mask``, ``post_valid`` and ``post_conf``."""
+
+    def __init__(self, model, graph=True, postprocess=None):
         self.model = model
+        self.post_kw = None
+        if postprocess is not None:
+            from .postprocess import post_kwargs
+            self.post_kw = post_kwargs(postprocess)
         self.side_stream = None
         self.graph = graph          # the pyramid as ONE graph launch per batch (static input / outputs) instead of ~60 eager launches
         self._g = self._g_key = self._g_in = self._g_out = None
@@ -787,7 +795,15 @@ class Evaluator:
         data_dict.pop("_fps_prefetch", None)
         if next_data is not None:
             self.prefetch(next_data)
-        return self.model(d, is_eval=True)
+        out = self.model(d, is_eval=True)
+        if self.post_kw is not None:
+            from .postprocess import detection_postprocess
+            post = detection_postprocess(out["point_clouds"], out["bbox_corner"], out["objectness_scores"], out["sem_cls"],
+                                         out["sem_cls_scores"], **self.post_kw)
+            for k, v in post.items():
+                if v is not None:
+                    out["post_" + k] = v
+        return out
 
 
 def synthetic_batch(batch: int, n_points: int, device, seed: int = 0, vocab: int = 3001, use_color=False,
