@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SPACAP_ABI_VERSION 4
+#define SPACAP_ABI_VERSION 5
 
 #define SPACAP_OK 0
 #define SPACAP_E_INVALID (-1)   /* bad argument (null pointer, negative size, unsupported shape) */
@@ -680,15 +680,13 @@ int spacap_dense_wgrad_tall_f32(const float *G, long ldg, const float *X, long l
  *   spacap_gemm_bf3_split_w_f32   Wp bf16 [3][N][K] = the three bf16 pieces of W f32 [N][K] (trans == 0, row stride ldw) or of the
  *                                 transpose of W f32 [K][N] (trans != 0); 3 N K two-byte elements
  *   spacap_gemm_bf3_f32           out f32 [R][N] (stride ldo) = A f32 [R][K] (stride lda) W^T + bias (nullable), ReLU when relu != 0
- *   spacap_gemm_bf3_wgrad_f32     part f32 [nslab][N][K]: per row slab dW[n][k] = sum_r G[r][n] X[r][k]; the caller adds the slabs
- *                                 in order; nslab = spacap_gemm_bf3_wgrad_slabs(R, N, K) or any count >= 1 */
+ *   spacap_gemm_bf3_wgrad_slabs   row slabs for the weight gradient dW [N][K] of such a layer over R rows: the nslab that the
+ *                                 relation head hands to spacap_linear_wgrad_nslab_f32 */
 int spacap_gemm_bf3_supported(int K, int N);
 int spacap_gemm_bf3_split_w_f32(const float *W, long ldw, int N, int K, int trans, void *Wp, spacap_stream_t stream);
 int spacap_gemm_bf3_f32(const float *A, long lda, const void *Wp, const float *bias, long R, int K, int N, int relu, float *out, long ldo,
                         spacap_stream_t stream);
 int spacap_gemm_bf3_wgrad_slabs(long R, int N, int K);
-int spacap_gemm_bf3_wgrad_f32(const float *G, long ldg, const float *X, long ldx, long R, int N, int K, int nslab, float *part,
-                              spacap_stream_t stream);
 /* Tail of the relation head's backward at any width C (C / 4 divides 256): dz2 f32 [R,C] = (dpred f32 [R,9] W3 f32 [9,C]) where
  * hid2 f32 [R,C] > 0, and per-workgroup partial sums part f32 [nparts][9 C + C + 16] = dW3 [9][C] | db2 [C] | db3 [9 (+7 pad)]. */
 int spacap_rel_wide_tail_supported(int C);

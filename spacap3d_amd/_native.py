@@ -15,7 +15,7 @@ import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libspacap_hip.so")
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _i = ctypes.c_int
 _l = ctypes.c_long
@@ -121,7 +121,6 @@ SIGNATURES = {
     "spacap_gemm_bf3_split_w_f32": (_i, [_p, _l, _i, _i, _i, _p, _p]),
     "spacap_gemm_bf3_f32": (_i, [_p, _l, _p, _p, _l, _i, _i, _i, _p, _l, _p]),
     "spacap_gemm_bf3_wgrad_slabs": (_i, [_l, _i, _i]),
-    "spacap_gemm_bf3_wgrad_f32": (_i, [_p, _l, _p, _l, _l, _i, _i, _i, _p, _p]),
     "spacap_rel_wide_tail_supported": (_i, [_i]),
     "spacap_rel_wide_tail_nparts": (_i, [_l]),
     "spacap_rel_wide_tail_bwd_f32": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _p]),

@@ -15,6 +15,7 @@
 // wave reduction on the value only, and the index is recovered by a second, rare pass that only the
 // wave(s) holding the maximum execute.  Two barriers per round.  Skipped / padded slots carry
 // temp = -1: fminf(d, -1) = -1 keeps them out of every arg-max exactly as the reference's `continue`.
+//   N <= 2 048   : coordinates in VGPRs and LDS, one barrier per round (fps_small_kernel)
 //   N <= 8 192   : coordinates in VGPRs too (fps_kernel)
 //   N <= 81 920  : Morton-bucketed scene, whole buckets skipped when provably unaffected (fps_bucket.inc)
 //   larger       : reference-style streaming with temp in the workspace (fps_generic_kernel)
@@ -125,56 +126,7 @@ __global__ __launch_bounds__(BLOCK) void fps_kernel(const float *__restrict__ xy
   }
 }
 
-// 512 < N <= 1 024 (the vote-aggregation sampling, 1 024 votes -> 256 proposals, sits on the step's critical path):
-// ONE wavefront per scene, 16 points per lane in registers, all coordinates also in LDS so that the new centre is an
-// LDS broadcast read instead of a dependent global load, the tie-break keys precomputed per slot, no barriers and
-// no atomics: 0.92 -> ~0.4 us per round.  Same selection rule as fps_kernel (first maximum in the reference's tree
-// order through fps_key).
-template <int TPL>
-__global__ __launch_bounds__(64) void fps_wave_kernel(const float *__restrict__ xyz_all, int N, int m, int lg,
-                                                      int32_t *__restrict__ idx_all) {
-  __shared__ float s_xyz[64 * TPL * 3];
-  const float *__restrict__ xyz = xyz_all + (size_t)blockIdx.x * N * 3;
-  int32_t *__restrict__ idxs = idx_all + (size_t)blockIdx.x * m;
-  const int lane = threadIdx.x;
-  for (int i = lane; i < N * 3; i += 64) s_xyz[i] = xyz[i];
-  float t[TPL], px[TPL], py[TPL], pz[TPL];
-  unsigned keys[TPL];
-#pragma unroll
-  for (int i = 0; i < TPL; ++i) {
-    const int k = lane + i * 64;
-    const int kk = k < N ? k : N - 1;
-    const float x = xyz[kk * 3 + 0], y = xyz[kk * 3 + 1], z = xyz[kk * 3 + 2];
-    const float mag = (x * x) + (y * y) + (z * z);
-    const bool skip = (k >= N) || ((double)mag <= 1e-3);
-    t[i] = skip ? -1.0f : 1e10f;
-    px[i] = x; py[i] = y; pz[i] = z;
-    keys[i] = fps_key(k, lg);
-  }
-  if (lane == 0) idxs[0] = 0;
-  __syncthreads();
-  int old = 0;
-  for (int j = 1; j < m; ++j) {
-    const float x1 = s_xyz[old * 3 + 0], y1 = s_xyz[old * 3 + 1], z1 = s_xyz[old * 3 + 2];
-    int lmax = __float_as_int(-1.0f);
-#pragma unroll
-    for (int i = 0; i < TPL; ++i) {
-      const float d = sqdist(px[i], py[i], pz[i], x1, y1, z1);
-      t[i] = vmin_f32(d, t[i]);
-      lmax = max(lmax, __float_as_int(t[i]));
-    }
-    const int M = wave_max_i32(lmax);
-    unsigned key = 0xFFFFFFFFu;
-#pragma unroll
-    for (int i = 0; i < TPL; ++i) key = (__float_as_int(t[i]) == M) ? min(key, keys[i]) : key;
-    key = wave_min_u32(key);
-    old = (M < 0) ? 0 : fps_unkey(key, lg);  // every point skipped: the reference returns index 0
-    old = __builtin_amdgcn_readfirstlane(old);
-    if (lane == 0) idxs[j] = old;
-  }
-}
-
-// N <= 8 192, the shape of every level below the first (2 048 -> 1 024 -> 512 -> 256) and of the vote-aggregation sampling
+// N <= 2 048, the shape of every level below the first (2 048 -> 1 024 -> 512 -> 256) and of the vote-aggregation sampling
 // (1 024 votes -> 256 proposals, on the step's critical path): ONE barrier per round and no dependent global load.
 //   * all coordinates also live in LDS as float4: the new centre is one broadcast ds_read_b128 (fps_kernel: three dependent
 //     global loads, ~0.2 us of every round);
@@ -183,7 +135,7 @@ __global__ __launch_bounds__(64) void fps_wave_kernel(const float *__restrict__ 
 //     reduces the NW records itself (two DPP reductions).
 // Same selection rule as fps_kernel: first maximum in the reference's tree order through fps_key; M < 0 (every point
 // skipped) gives index 0.  Rounds: 0.75 -> 0.57 us at N = 2 048, 0.62 -> 0.50 us at N = 1 024, 0.39 at 512, 0.32 at 256: a
-// single wave costs 0.28 us + 17 ns per point slot and round (tools/lab/fps_small_bench.py).
+// single wave costs 0.28 us + 17 ns per point slot and round.
 template <int BLOCK, int TPL>
 __global__ __launch_bounds__(BLOCK) void fps_small_kernel(const float *__restrict__ xyz_all, int N, int m, int lg,
                                                           int32_t *__restrict__ idx_all) {
@@ -366,36 +318,21 @@ extern "C" int spacap_fps_f32(const float *xyz, int B, int N, int m, void *works
     SPACAP_CHECK_LAUNCH("spacap_fps_f32");                     \
     return SPACAP_OK;                                          \
   }
-  // SPACAP_FPS_LEGACY=1 (tests / lab): the round-5 kernels (fps_kernel, fps_wave_kernel) instead of fps_small_kernel
-  static const bool legacy = getenv("SPACAP_FPS_LEGACY") != nullptr && atoi(getenv("SPACAP_FPS_LEGACY")) != 0;
-  if (!legacy && N <= 2048) {
 #define FPS_SMALL(BLOCK, TPL)                                                                          \
   if (N <= (BLOCK) * (TPL)) {                                                                          \
     SPACAP_CHECK_HIP((launch_fps_small<BLOCK, TPL>(xyz, B, N, m, lg, idx, s)), "spacap_fps_f32(small)"); \
     SPACAP_CHECK_LAUNCH("spacap_fps_f32(small)");                                                      \
     return SPACAP_OK;                                                                                  \
   }
-    // (measured per shape, tools/lab/fps_small_bench.py; beyond 2 048 points the two-barrier kernel with its rare second pass
-    // is the faster one: 16 waves pay 3 VALU per point for keys that one wave needs)
-    FPS_SMALL(64, 1)
-    FPS_SMALL(64, 2)
-    FPS_SMALL(64, 4)
-    FPS_SMALL(64, 8)
-    FPS_SMALL(256, 4)
-    FPS_SMALL(512, 4)
+  // (measured per shape; beyond 2 048 points the two-barrier kernel with its rare second pass is the faster one: 16 waves
+  // pay 3 VALU per point for keys that one wave needs)
+  FPS_SMALL(64, 1)
+  FPS_SMALL(64, 2)
+  FPS_SMALL(64, 4)
+  FPS_SMALL(64, 8)
+  FPS_SMALL(256, 4)
+  FPS_SMALL(512, 4)
 #undef FPS_SMALL
-  }
-  FPS_CASE(64, 1)
-  FPS_CASE(64, 2)
-  FPS_CASE(64, 4)
-  FPS_CASE(64, 8)
-  if (N <= 1024) {
-    hipLaunchKernelGGL((fps_wave_kernel<16>), dim3(B), dim3(64), 0, s, xyz, N, m, lg, idx);
-    SPACAP_CHECK_LAUNCH("spacap_fps_f32(wave)");
-    return SPACAP_OK;
-  }
-  FPS_CASE(256, 4)
-  FPS_CASE(256, 8)
   FPS_CASE(1024, 4)
   FPS_CASE(1024, 8)
 #undef FPS_CASE
@@ -409,23 +346,4 @@ extern "C" int spacap_fps_f32(const float *xyz, int B, int N, int m, void *works
   hipLaunchKernelGGL((fps_generic_kernel<1024>), dim3(B), dim3(1024), 0, s, xyz, ws, N, m, lg, idx);
   SPACAP_CHECK_LAUNCH("spacap_fps_f32(generic)");
   return SPACAP_OK;
-}
-
-// LAB (tools/lab/fps_small_bench.py; not declared in the public header): fps_small_kernel at a chosen workgroup shape
-extern "C" int spacap_lab_fps_small(const float *xyz, int B, int N, int m, int block, int tpl, int32_t *idx, spacap_stream_t stream) {
-  SPACAP_REQUIRE(xyz && idx && B >= 1 && N >= 1 && m >= 1 && N <= 8192 && N <= block * tpl, "spacap_lab_fps_small: bad arguments");
-  hipStream_t s = spacap::as_stream(stream);
-  const int bs = spacap_opt_n_threads(N);
-  int lg = 0;
-  while ((1 << lg) < bs) ++lg;
-#define V(BL, TP)                                                                                             \
-  if (block == BL && tpl == TP) {                                                                             \
-    SPACAP_CHECK_HIP((launch_fps_small<BL, TP>(xyz, B, N, m, lg, idx, s)), "spacap_lab_fps_small");           \
-    SPACAP_CHECK_LAUNCH("spacap_lab_fps_small");                                                              \
-    return SPACAP_OK;                                                                                         \
-  }
-  V(64, 1) V(64, 2) V(64, 4) V(64, 8) V(64, 16) V(128, 2) V(128, 4) V(128, 8) V(256, 1) V(256, 2) V(256, 4) V(256, 8) V(512, 1) V(512, 2)
-  V(512, 4) V(1024, 1) V(1024, 2) V(1024, 4) V(1024, 8)
-#undef V
-  SPACAP_REQUIRE(false, "spacap_lab_fps_small: (%d, %d) not instantiated", block, tpl);
 }

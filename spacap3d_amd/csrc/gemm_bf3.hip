@@ -19,10 +19,8 @@
 // buffer, two barriers per step); two workgroups per CU (61 KB of LDS, <= 256 registers) overlap each other's staging and matrix
 // phases.  Workgroup -> tile mapping: the column tiles of one row tile run back to back ON THE SAME XCD (workgroups are dealt
 // round robin to the 8 XCDs), so an activation tile is fetched from HBM once and re-read from that XCD's L2.
-// Epilogues: bias + ReLU (forward); none (data gradient: the consumer masks).  Split over rows for the weight gradient
-//     dW[n, k] = sum_r G[r, n] X[r, k]
-// (contraction over the rows: both operands are staged TRANSPOSED, channel-major bf16 images, so that the matrix cores read 16
-// bytes of consecutive rows per lane); per-slab partial results, added in slab order by the caller.
+// Epilogues: bias + ReLU (forward); none (data gradient: the consumer masks).  The weight gradient runs on the Linear layers'
+// split-bf16 kernel (csrc/wgrad_bf3.inc); spacap_gemm_bf3_wgrad_slabs sizes its row slabs for the relation head.
 #include "common.hpp"
 
 namespace {
@@ -151,89 +149,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf3_kernel(const float *__restric
         if (r < R) out[(size_t)r * ldo + c] = v;
       }
   }
-}
-
-// ---- weight gradient: part[slab][n][k] = sum over the slab's rows of G[r][n] X[r][k] ------------------------------------------
-// 128 (n) x 128 (k) tile of dW per workgroup, rows in steps of 32 (= the contraction depth of one MFMA).  Both operands arrive
-// row-major (a thread: 16 consecutive channels of one row) and are needed channel-major (a lane: 8 consecutive rows of one
-// channel): the split pieces are written to LDS transposed, two bytes at a time, into [128 channels][32 + 8 rows] images.
-constexpr int LDT_ROW = 32 + 8;   // halfs per channel row of a transposed image (80 bytes: conflict-free 16-byte reads)
-__global__ __launch_bounds__(256, 2) void gemm_bf3_wgrad_kernel(const float *__restrict__ G, long ldg, const float *__restrict__ X, long ldx,
-                                                                long R, int N, int K, float *__restrict__ part) {
-  __shared__ __attribute__((aligned(16))) __bf16 sG[3 * 128 * LDT_ROW];
-  __shared__ __attribute__((aligned(16))) __bf16 sX[3 * 128 * LDT_ROW];
-  constexpr int TIMG = 128 * LDT_ROW;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
-  const int wm = w >> 1, wn = w & 1;
-  const int n0 = blockIdx.y * 128, k0 = blockIdx.z * 128;
-  const int nslab = gridDim.x;
-  const long nsteps = (R + 31) / 32, per = (nsteps + nslab - 1) / nslab;
-  const long sbeg = (long)blockIdx.x * per, send = sbeg + per < nsteps ? sbeg + per : nsteps;
-  // staging: thread = (row tid / 8 of the 32-row step, channel pairs 2 (tid % 8) + 16 i, i < 8): 8-byte loads, 64 contiguous bytes
-  // per 8 lanes; the transposed two-byte LDS writes of a wave then fall into 32 distinct words (channel pitch 20 words: the 8
-  // lanes of a row are 40 words apart, the 8 rows of a wave share 4 words)
-  const int srow = tid >> 3, sq = 2 * (tid & 7);
-  float2 rg[8], rx[8];
-  auto fetch = [&](long s) {
-    const long r = s * 32 + srow;
-    const bool ok = s < send && r < R;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      rg[i] = ok ? *reinterpret_cast<const float2 *>(G + (size_t)r * ldg + n0 + sq + 16 * i) : make_float2(0.f, 0.f);
-      rx[i] = ok ? *reinterpret_cast<const float2 *>(X + (size_t)r * ldx + k0 + sq + 16 * i) : make_float2(0.f, 0.f);
-    }
-  };
-  auto put = [&](__bf16 *img, const float2 *v) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const float x = u ? v[i].y : v[i].x;
-        const __bf16 h = (__bf16)x;
-        const float r1 = x - (float)h;
-        const __bf16 m = (__bf16)r1;
-        __bf16 *d = img + (sq + 16 * i + u) * LDT_ROW + srow;
-        d[0] = h, d[TIMG] = m, d[2 * TIMG] = (__bf16)(r1 - (float)m);
-      }
-    }
-  };
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  fetch(sbeg);
-  for (long s = sbeg; s < send; ++s) {
-    __syncthreads();
-    put(sG, rg);
-    put(sX, rx);
-    __syncthreads();
-    fetch(s + 1);
-    bf16x8 a[4][3];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) a[mt][p] = *reinterpret_cast<const bf16x8 *>(sG + p * TIMG + (64 * wm + 16 * mt + l15) * LDT_ROW + 8 * lg);
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      bf16x8 b[3];
-#pragma unroll
-      for (int p = 0; p < 3; ++p) b[p] = *reinterpret_cast<const bf16x8 *>(sX + p * TIMG + (64 * wn + 16 * nt + l15) * LDT_ROW + 8 * lg);
-      constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
-#pragma unroll
-      for (int q = 0; q < 6; ++q)
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) acc[mt][nt] = MFMA_B(a[mt][PA[q]], b[PB[q]], acc[mt][nt]);
-    }
-  }
-  float *o = part + (size_t)blockIdx.x * N * K;
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        o[(size_t)(n0 + 64 * wm + 16 * mt + 4 * lg + u) * K + k0 + 64 * wn + 16 * nt + l15] = acc[mt][nt][u];
 }
 
 // ---- tail of the relation head's backward at any width C (multiple of 4, C / 4 dividing 256):
@@ -552,7 +467,7 @@ extern "C" int spacap_gemm_bf3_f32(const float *A, long lda, const void *Wp, con
   return SPACAP_OK;
 }
 
-/* row slabs (= partial results) of spacap_gemm_bf3_wgrad_f32 for (R, N, K) */
+/* row slabs (= partial results) of the relation head's weight gradient (spacap_linear_wgrad_nslab_f32) for (R, N, K) */
 extern "C" int spacap_gemm_bf3_wgrad_slabs(long R, int N, int K) {
   if (R < 1 || !bf3_shape(K, N)) return 0;
   const long steps = (R + 31) / 32, yz = (long)(N / 128) * (K / 128);
@@ -560,19 +475,6 @@ extern "C" int spacap_gemm_bf3_wgrad_slabs(long R, int N, int K) {
   if (n > cap) n = cap;
   if (n > steps / 8) n = steps / 8;
   return (int)(n < 1 ? 1 : n);
-}
-
-/* part f32 [nslab][N][K]: per row slab, dW[n][k] = sum_r G[r][n] X[r][k] (G f32 [R][N] at stride ldg, X f32 [R][K] at stride
-   ldx, 16-byte aligned rows); the caller adds the slabs in order.  N, K multiples of 128. */
-extern "C" int spacap_gemm_bf3_wgrad_f32(const float *G, long ldg, const float *X, long ldx, long R, int N, int K, int nslab, float *part,
-                                         spacap_stream_t stream) {
-  const char *what = "spacap_gemm_bf3_wgrad_f32";
-  SPACAP_REQUIRE(R >= 1 && bf3_shape(K, N) && nslab >= 1 && nslab <= 65535 && ldg >= N && ldx >= K && ldg % 4 == 0 && ldx % 4 == 0,
-                 "%s: (R=%ld, N=%d, K=%d, nslab=%d) unsupported", what, R, N, K, nslab);
-  SPACAP_REQUIRE(G && X && part && ((reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(X)) & 15) == 0, "%s: null / unaligned pointer", what);
-  hipLaunchKernelGGL(gemm_bf3_wgrad_kernel, dim3(nslab, N / 128, K / 128), dim3(256), 0, spacap::as_stream(stream), G, ldg, X, ldx, R, N, K, part);
-  SPACAP_CHECK_LAUNCH(what);
-  return SPACAP_OK;
 }
 
 /* ---- tail of the relation head's backward at any width (see rel_wide_tail_bwd_kernel) ---------------------------------------

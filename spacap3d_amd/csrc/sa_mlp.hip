@@ -773,9 +773,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(L1 ? 2 : 1)
         if (L.feat) in[3] = L.feat[(size_t)b * L.Np + p];
       }
       st4(&s_rel[tid * 4], in);
-#ifndef SPACAP_HACK_NOQ3
       q2 += in;
-#endif
     }
     __syncthreads();
     if (PREFETCH && FULL) fetch(t + gridDim.x);
@@ -823,9 +821,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(L1 ? 2 : 1)
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             q1[u] += in * d[u];
-#ifndef SPACAP_HACK_NOQ3
             q3[u] += in * z[u];
-#endif
           }
         } else {
           st4(dyp + o, d);
@@ -1340,8 +1336,6 @@ inline int device_cus() {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
     (void)hipGetLastError();
-    // LAB: the CUs the step's stream may use when it was created with a CU mask (tools/lab/cumask_step.py)
-    if (const char *e = getenv("SPACAP_LAB_CUS")) { const int v = atoi(e); if (v >= 8 && v <= cus) cus = v; }
     return cus;
   }();
   return n;
@@ -1365,11 +1359,8 @@ inline int fwd_resident(int resident) {
 // The BACKWARD kernels with persistent grids leave the reserved CUs out as well: the sampling chain of the next batch now runs
 // beside the first ~5.8 ms of a ~7.4 ms step, i.e. beside the captioner's and most of the detector's backward, and a whole-CU
 // workgroup that finds its CU taken runs as a second round (tools/lab/beside.py: 1.5 - 1.9x beside ANY 8 resident workgroups).
-// (LAB knob SPACAP_LAB_BWD_RESERVE: 0 = full grids as before, 1 = per-CU count x reserved, 3 = the forward formula)
+// They leave out (resident workgroups per CU) x (reserved CUs).
 inline int bwd_resident(int resident) {
-  static const int mode = [] { const char *e = getenv("SPACAP_LAB_BWD_RESERVE"); return e ? atoi(e) : 1; }();
-  if (mode == 0) return resident;
-  if (mode == 3) return fwd_resident(resident);
   const int per = resident / device_cus();
   return resident - per * reserved_cus();
 }

@@ -26,11 +26,7 @@ def _role_stream(device, role):
     key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
     if key not in _STREAMS:
         dev = torch.device("cuda", key[1])
-        # (lab switch: a high-priority side stream changes nothing in the usual placement and makes the bad one worse,
-        # tools/lab/quick_config_steps.py)
-        prio = int(os.environ.get("SPACAP_SIDE_PRIORITY", "0"))
-        _STREAMS[key] = {r: torch.cuda.Stream(device=dev, priority=prio if r == "side" else 0)
-                         for r in ("side", "capture", "comm", "wgrad", "relation")}
+        _STREAMS[key] = {r: torch.cuda.Stream(device=dev) for r in ("side", "capture", "comm", "wgrad", "relation")}
     return _STREAMS[key][role]
 
 
@@ -586,7 +582,7 @@ class Trainer:
             return False
 
     # CUs the relation head's grids leave to the decoder running beside it (below 56 the two chains serialise again: measured)
-    RELATION_LEAVE_CUS = int(os.environ.get("SPACAP_RELATION_LEAVE_CUS", "64"))
+    DECODER_CUS = 64
 
     def _fork_relation(self, dev, armed=None):
         """Inside this Trainer's steps the relation head (forward 0.16 ms, backward 0.46 ms of persistent workgroups) and the caption
@@ -600,7 +596,7 @@ class Trainer:
         for mod in self.model.modules():
             if isinstance(mod, TransformerDecoderModel):
                 mod.fork_relation = on
-        check(lib.spacap_relation_fused_leave_cus(self.RELATION_LEAVE_CUS if on else 0), "spacap_relation_fused_leave_cus")
+        check(lib.spacap_relation_fused_leave_cus(self.DECODER_CUS if on else 0), "spacap_relation_fused_leave_cus")
 
     def _capture(self, static, warmup):
         """``warmup`` REAL training steps on the static batch (they update the parameters, the BatchNorm statistics

@@ -7,8 +7,6 @@ GEMM, see _forward_product); the backward's
 ``dW = g^T x`` and ``db = sum_r g`` -- for <= 2 048 rows a memset + a split-K GEMM + a column-sum kernel of
 ~30 us of latency -- become one kernel producing per-slab partials of both plus one sum over the slabs.
 """
-import os
-
 import torch
 import torch.nn.functional as F
 from torch.autograd import Function
@@ -227,25 +225,20 @@ def packed_views(flat, params_w, params_b):
     return flat[ow:ow + rows * cols].view(rows, cols), flat[ob:ob + rows]
 
 
-# wide relation head (d_model = 512): weight gradient by csrc/wgrad_bf3.inc instead of gemm_bf3_wgrad_kernel (lab switch)
-WIDE_WGRAD_TR = os.environ.get("SPACAP_WIDE_WGRAD_TR", "1") != "0"
-
-
 class Conv1x1(Function):
     """nn.Conv1d / nn.Conv2d with a 1x1 kernel on channel-major (B, C, N[, 1]) tensors -- the vote net and the
     feature-propagation MLPs (models/voting_module.py:33-60, lib/pointnet2/pointnet2_modules.py:376-421), the proposal head and the
-    position embedding.  Forward (bias in the epilogue) and input gradient: csrc/conv1x1.hip (USE_OWN_CONV; point counts that are
-    not a multiple of 64 fall back to the convolution library); weight gradient: csrc/sa_mlp.hip: conv1x1_wgrad_kernel + one sum
+    position embedding.  Forward (bias in the epilogue) and input gradient: csrc/conv1x1.hip (point counts that are not a
+    multiple of 64 fall back to the convolution library); weight gradient: csrc/sa_mlp.hip: conv1x1_wgrad_kernel + one sum
     over its slabs."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
-        if USE_OWN_CONV:
-            y = conv1x1_cm(0, weight, x, bias, weight.shape[0])
-            if y is not None:
-                return y
+        y = conv1x1_cm(0, weight, x, bias, weight.shape[0])
+        if y is not None:
+            return y
         return F.conv2d(x, weight, bias) if x.dim() == 4 else F.conv1d(x, weight, bias)
 
     @staticmethod
@@ -257,7 +250,7 @@ class Conv1x1(Function):
         g = g.contiguous()
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = conv1x1_cm(1, weight, g, None, CI) if USE_OWN_CONV else None
+            dx = conv1x1_cm(1, weight, g, None, CI)
             if dx is None:
                 dx = torch.ops.aten.convolution_backward(g, x, weight, None, [1] * (x.dim() - 2), [0] * (x.dim() - 2),
                                                          [1] * (x.dim() - 2), False, [0] * (x.dim() - 2), 1,
@@ -282,9 +275,7 @@ class Conv1x1(Function):
 # Forward and input gradient of these convolutions run on the library's own channel-major kernel (csrc/conv1x1.hip, bias in
 # its epilogue; gated against float64 in tests/test_attention_gpu.py::test_conv1x1_channel_major_kernel).  Rounds 2 - 3 kept them
 # on MIOpen / rocBLAS because the kernel's summation order moved a chaotic 5-step trajectory gate; that gate now freezes the
-# discrete selections it cannot control (tests/test_engine_gpu.py) and a re-association passes it.  False restores the library
-# calls (A/B measurements).
-USE_OWN_CONV = True
+# discrete selections it cannot control (tests/test_engine_gpu.py) and a re-association passes it.
 # tests: the forward on the fp32-MFMA kernel (exact fp32 products) instead of the split-bf16 one -- for comparisons of two paths
 # whose discrete selections (ReLU gates, pooling arg-max) must not see a 1e-6 difference in a pre-activation
 CONV_FWD_EXACT_F32 = False
@@ -319,7 +310,7 @@ def conv1x1(x, conv):
     needs = torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad
                                          or (conv.bias is not None and conv.bias.requires_grad))
     if not needs:
-        return conv1x1_cm(0, conv.weight, x, conv.bias, conv.out_channels) if USE_OWN_CONV else None
+        return conv1x1_cm(0, conv.weight, x, conv.bias, conv.out_channels)
     B, CI = x.shape[0], x.shape[1]
     N = x.numel() // max(B * CI, 1)
     if int(lib.spacap_conv1x1_wgrad_slabs(B, conv.out_channels, CI, N)) == 0:
@@ -496,14 +487,10 @@ class RelationWide(Function):
             dW3, db2, db3 = s[:NO * C].view(NO, C), s[NO * C:NO * C + C], s[NO * C + C:NO * C + C + NO]
             nslab = int(lib.spacap_gemm_bf3_wgrad_slabs(R, C, C))
             pw = torch.empty(nslab, C * C, dtype=torch.float32, device=dev)
-            if WIDE_WGRAD_TR:
-                # the Linear layers' split-bf16 weight-gradient kernel (row-major images read by transposing LDS reads:
-                # csrc/wgrad_bf3.inc) instead of gemm_bf3_wgrad_kernel's images staged transposed with two-byte LDS writes
-                check(lib.spacap_linear_wgrad_nslab_f32(dz2.data_ptr(), hid1.data_ptr(), R, C, C, 0, nslab, pw.data_ptr(), st),
-                      "spacap_linear_wgrad_nslab_f32")
-            else:
-                check(lib.spacap_gemm_bf3_wgrad_f32(dz2.data_ptr(), C, hid1.data_ptr(), C, R, C, C, nslab, pw.data_ptr(), st),
-                      "spacap_gemm_bf3_wgrad_f32")
+            # the Linear layers' split-bf16 weight-gradient kernel (row-major images read by transposing LDS reads:
+            # csrc/wgrad_bf3.inc)
+            check(lib.spacap_linear_wgrad_nslab_f32(dz2.data_ptr(), hid1.data_ptr(), R, C, C, 0, nslab, pw.data_ptr(), st),
+                  "spacap_linear_wgrad_nslab_f32")
             dW2 = sum_slabs(pw, deferrable=True).view(C, C)
             dh1 = bf3_product(dz2, bf3_pieces(W2, trans=True), out=hid2)      # hid2 is dead: its memory takes dhid1
             del dz2

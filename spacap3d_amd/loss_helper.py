@@ -13,7 +13,6 @@ Restated so that one training step needs NO host synchronisation:
 """
 import math
 
-import os
 import torch
 import torch.nn.functional as F
 
@@ -25,9 +24,6 @@ OBJECTNESS_CLS_WEIGHTS = [0.2, 0.8]
 
 _CONST = {}
 
-
-# lab switch (same-box A/B): the fused relation loss on the relation head's stream when the head was forked
-REL_LOSS_ON_ITS_STREAM = os.environ.get("SPACAP_REL_LOSS_FORKED", "1") != "0"
 
 def _const(key, device, build):
     """Device-resident constants are built once per device (a host -> device copy is not allowed while a
@@ -246,7 +242,7 @@ def get_scene_cap_loss(data_dict, device=None, config=None, detection=True, capt
     if use_relation:
         from .backend import ops
         frel = getattr(ops(), "relation_losses", None) if d["relation_pred"].is_cuda else None
-        if rel_stream is not None and frel is not None and det_early and REL_LOSS_ON_ITS_STREAM:
+        if rel_stream is not None and frel is not None and det_early:
             # The relation loss stays on the head's stream: its forward (0.03 ms) then runs beside the decoder instead of after it,
             # and its backward is followed by the head's backward kernel on the same stream without a cross-stream wait.  Everything
             # it reads besides relation_pred (labels, the detection losses' object assignment) exists since before the fork.

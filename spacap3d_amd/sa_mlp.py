@@ -6,8 +6,6 @@ lib/pointnet2/pytorch_utils.py:11-36).  See ``csrc/sa_mlp.hip`` for the kernels 
 The grouping indices come from ``ball_query`` as before; eval mode and MLP shapes without kernels keep using
 the per-operator path (``QueryAndGroup`` + ``SharedMLP``), which is also HIP.
 """
-import os
-
 import torch
 from torch.autograd import Function
 
@@ -20,16 +18,15 @@ RECOMPUTE_Z1 = True
 # ... and take that layer's BatchNorm statistics from the first and second moments of the rows' four inputs (z1 is linear in
 # them): 14 sums per row, one thread per row, instead of 2 x 64 sums with 16 threads per row (csrc/sa_mlp.hip:
 # sa_l1_moments_kernel; 87 -> ~20 us at SA1).  The statistics differ from the summed-z1 form by rounding only (~1e-7 relative).
-L1_MOMENTS = os.environ.get("SPACAP_SA_L1_MOMENTS", "1") not in ("", "0")
+L1_MOMENTS = True
 # pooled last layer: its WEIGHT gradient from z2 alone (csrc/sa_l3bwd.inc: sa_wgrad_pool_kernel -- the sparse
 # term (g d)^T a2 plus the Gram matrix a2^T a2) instead of the dense kernel that streams z3 and z2 and multiplies a [C3 x rows]
 # operand with one non-zero per group and channel.  SA1: 92 + 12 us against 249 + 12 us (tools/lab/wgrad_pool_bench.py).  Used
 # from POOL_WGRAD_MIN_ROWS rows on (below, the two extra launches of the reduction cost more than the pass saves).
-POOL_WGRAD = os.environ.get("SPACAP_SA_POOL_WGRAD", "1") not in ("", "0")
+POOL_WGRAD = True
 POOL_WGRAD_MIN_ROWS = 131072
-# SA1's second layer: weight gradient from the data-gradient kernel's pass (tests / lab: SPACAP_SA_FUSE_L2_WGRAD=0 keeps the two
-# kernels apart)
-FUSE_L2_WGRAD = os.environ.get("SPACAP_SA_FUSE_L2_WGRAD", "1") not in ("", "0")
+# SA1's second layer: weight gradient from the data-gradient kernel's pass (tests: False keeps the two kernels apart)
+FUSE_L2_WGRAD = True
 
 
 def _ptr(t):

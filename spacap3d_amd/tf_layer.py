@@ -14,7 +14,6 @@ activations h) is consumed only by ``Ffn2Ln``, whose backward hands back the gra
 PRE-activation (relu / dropout mask already applied, one fused launch); ``AttnOutFfn1.backward`` expects exactly that.
 """
 import ctypes
-import os
 
 import torch
 from torch.autograd import Function
@@ -22,9 +21,8 @@ from torch.autograd import Function
 from ._native import TfRowsArgs, check, grad_slot, lib, linear_wgrad_partials, sum_slabs
 
 D_MODEL = 128
-# tests / A-B measurements switch the fused stacks off here (the per-operator path of transformer_captioner.py then runs)
-SPLIT_MAX = int(os.environ.get("SPACAP_TF_SPLIT_MAX", "0"))   # lab knob: cap on the K slices of the split products
-ENABLED = os.environ.get("SPACAP_TF_FUSED", "1") != "0"   # (A/B runs of bench.py)
+# tests switch the fused stacks off here (the per-operator path of transformer_captioner.py then runs)
+ENABLED = True
 
 
 def supported(d_model, d_ff):
@@ -70,8 +68,6 @@ def _split_product(a2, W, trans_w):
     R, K = a2.shape
     dev = a2.device
     S = int(lib.spacap_tf_gemm_splits(R, K, D_MODEL))
-    if SPLIT_MAX:
-        S = max(d for d in range(1, min(S, SPLIT_MAX) + 1) if (K // 128) % d == 0)
     parts = _new(dev, S, R, D_MODEL)
     check(lib.spacap_tf_gemm_f32(a2.data_ptr(), W.data_ptr(), R, K, D_MODEL, 1 if trans_w else 0, S, parts.data_ptr(),
                                  torch.cuda.current_stream(dev).cuda_stream), "spacap_tf_gemm_f32")

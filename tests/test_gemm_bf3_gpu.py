@@ -41,15 +41,17 @@ def test_tiled_split_bf16_product(lin, R, K, N, trans, relu):
     assert _rel(Wp, W.double().t() if trans else W.double()) < 2e-7
 
 
-@pytest.mark.parametrize("R,N,K", [(65536, 512, 512), (5000, 128, 256), (33, 256, 128)])
+# (the weight gradient of RelationWide: spacap_linear_wgrad_nslab_f32 with the slab count of spacap_gemm_bf3_wgrad_slabs; it takes
+# at most one slab per 32 rows, so the ragged small shape has 129 rows = 5 tiles, the last one of a single row)
+@pytest.mark.parametrize("R,N,K", [(65536, 512, 512), (5000, 128, 256), (129, 256, 128)])
 def test_tiled_split_bf16_weight_gradient(R, N, K):
     from spacap3d_amd._native import check, lib
     g = torch.Generator().manual_seed(R + N)
     G, X = torch.randn(R, N, generator=g).to(DEV), (torch.randn(R, K, generator=g) + 0.2).to(DEV)
     for ns in {int(lib.spacap_gemm_bf3_wgrad_slabs(R, N, K)), 1, 5}:
         part = torch.full((ns, N * K), float("nan"), device=DEV)
-        check(lib.spacap_gemm_bf3_wgrad_f32(G.data_ptr(), N, X.data_ptr(), K, R, N, K, ns, part.data_ptr(),
-                                            torch.cuda.current_stream().cuda_stream), "spacap_gemm_bf3_wgrad_f32")
+        check(lib.spacap_linear_wgrad_nslab_f32(G.data_ptr(), X.data_ptr(), R, N, K, 0, ns, part.data_ptr(),
+                                                torch.cuda.current_stream().cuda_stream), "spacap_linear_wgrad_nslab_f32")
         ref = G.double().t() @ X.double()
         assert _rel(part.double().sum(0).view(N, K), ref) < (1e-5 if ns > 1 or R < 10000 else 1e-4), ns
 
