@@ -21,6 +21,7 @@
 #include <atomic>
 
 #include "common.hpp"
+#include "mfma.hpp"
 
 namespace {
 // element index of the float4 group i of channel c: (i / per_b) rows of C * L + (i % per_b) * 4.  i and per_b fit 32 bits on every
@@ -36,7 +37,7 @@ __device__ __forceinline__ size_t group_off(long i, long per_b, int C, int c, lo
   return ((size_t)b * C + c) * L + (size_t)l4 * 4;
 }
 
-using f32x4 = float __attribute__((ext_vector_type(4)));
+using spacap::mfma::f32x4;
 constexpr int STAT_THREADS = 256;
 
 __device__ __forceinline__ double block_sum_f64(double v, double *s_buf) {

@@ -15,13 +15,11 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "mfma.hpp"
 
 namespace {
 
-using f32x4 = float __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-__device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
+using namespace spacap::mfma;
 
 constexpr int TM = 64, TN = 64, KC = 32, LDN = TN + 4, LDW = TM + 4;
 
@@ -121,38 +119,14 @@ __global__ __launch_bounds__(256) void conv1x1_cm_kernel(const float *__restrict
 // The fp32-MFMA kernel above is matrix-pipe bound (1 GFLOP per layer at 1/16 of the bf16 rate, 20 us for 7.8 us of matrix
 // time).  Here both operands are split into three bf16 pieces (x = x1 + x2 + x3, 24 significant bits) on their way in and a
 // product is the six piece products above 2^-24 on v_mfma_f32_16x16x32_bf16 (6/16 of the fp32-MFMA time; the arithmetic of
-// sa_bf3.inc / relation_fused.hip / wgrad_bf3.inc).  The activation chunk [32 k][64 n] stays row-major in LDS (n contiguous, as
+// sa_bf3.inc / relation_fused.hip / linear_grad.hip).  The activation chunk [32 k][64 n] stays row-major in LDS (n contiguous, as
 // in memory) and the B fragments -- 8 consecutive k of one column n -- come out of it through ds_read_b64_tr_b16, the
 // transposing LDS read of gfx950; the forward's weights are split in registers (a lane's 8 consecutive k of its row), the
 // input gradient's W^T chunk goes through a second image that is read the same way.  Same tiling, grid and C layout as above.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 constexpr int BLD = TN + 8;                // bf16 elements per image row (144 bytes)
 constexpr int BIMG = KC * BLD;             // one piece of one chunk
 
-__device__ __forceinline__ void split4(f32x4 v, bf16x4 &p0, bf16x4 &p1, bf16x4 &p2) {
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const __bf16 h = (__bf16)v[u];
-    const float r = v[u] - (float)h;
-    const __bf16 m = (__bf16)r;
-    p0[u] = h, p1[u] = m, p2[u] = (__bf16)(r - (float)m);
-  }
-}
-// 16x16x32 fragment whose 16 outer indices are the image columns c0 .. c0 + 15 and whose contraction index is the chunk's 32
-// rows: lane (g = lane >> 4, i = lane & 15) gets rows 8 g .. 8 g + 7 of column c0 + i (two transposing reads of 4 rows each;
-// lane 4 q + p of a group supplies the address of row q, columns 4 p .. 4 p + 3 of the block)
-__device__ __forceinline__ bf16x8 tr_frag(const __bf16 *img, int c0, int lane) {
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-  const __bf16 *a = img + (8 * g + q) * BLD + c0 + 4 * p;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(a));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(a + 4 * BLD));
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
+// (split4 and the transposing fragment read tr_frag<BLD>: mfma.hpp)
 
 template <bool TRANS_A>
 __global__ __launch_bounds__(256) void conv1x1_cm_bf3_kernel(const float *__restrict__ W, int lda, const float *__restrict__ in,
@@ -243,16 +217,15 @@ __global__ __launch_bounds__(256) void conv1x1_cm_bf3_kernel(const float *__rest
     __syncthreads();   // chunk c is in LDS (and chunk c - 1's readers were done before its buffer was written again)
     if (TRANS_A) {
 #pragma unroll
-      for (int q = 0; q < 3; ++q) a[q] = tr_frag(&s_a[buf * 3 * BIMG + q * BIMG], 16 * w, lane);
+      for (int q = 0; q < 3; ++q) a[q] = tr_frag<BLD>(&s_a[buf * 3 * BIMG + q * BIMG], 16 * w, lane);
     }
-    constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};   // the six products above 2^-24, smallest first
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       bf16x8 bq[3];
 #pragma unroll
-      for (int q = 0; q < 3; ++q) bq[q] = tr_frag(&s_b[buf][q * BIMG], 16 * t, lane);
+      for (int q = 0; q < 3; ++q) bq[q] = tr_frag<BLD>(&s_b[buf][q * BIMG], 16 * t, lane);
 #pragma unroll
-      for (int q = 0; q < 6; ++q) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[PA[q]], bq[PB[q]], acc[t], 0, 0, 0);
+      for (int q = 0; q < 6; ++q) acc[t] = MFMA_B(a[PA[q]], bq[PB[q]], acc[t]);   // (PA, PB: mfma.hpp)
     }
   }
   // acc[t][u] = C[m0 + 16 w + 4 lg + u][n0 + 16 t + l15]
@@ -266,12 +239,6 @@ __global__ __launch_bounds__(256) void conv1x1_cm_bf3_kernel(const float *__rest
       for (int t = 0; t < 4; ++t) o[16 * t] = acc[t][u] + bv;
     }
   }
-}
-
-// SPACAP_SA_F32MFMA=1 (the library's one switch, sa_mlp.hip) keeps the fp32-MFMA kernel
-inline bool conv_f32_mfma_only() {
-  static const bool on = getenv("SPACAP_SA_F32MFMA") != nullptr && atoi(getenv("SPACAP_SA_F32MFMA")) != 0;
-  return on;
 }
 
 }  // namespace
@@ -296,7 +263,7 @@ extern "C" int spacap_conv1x1_cm_f32(int mode, const float *W, const float *in, 
   hipStream_t s = spacap::as_stream(stream);
   // measured in the step (cfg2, 12 + 12 launches): forward 219 -> 192 us on the split-bf16 kernel; the input gradient, whose W^T
   // chunk must be split and staged as a second image, 232 -> 246 us: it stays on the fp32-MFMA kernel
-  if (mode == 0 && !f32fwd && !conv_f32_mfma_only())
+  if (mode == 0 && !f32fwd && !spacap::sa_f32_mfma_only())
     hipLaunchKernelGGL(conv1x1_cm_bf3_kernel<false>, grid, dim3(256), 0, s, W, CI, in, bias, M, K, (int)N, out);
   else if (mode == 0) hipLaunchKernelGGL(conv1x1_cm_kernel<false>, grid, dim3(256), 0, s, W, CI, in, bias, M, K, (int)N, out);
   else hipLaunchKernelGGL(conv1x1_cm_kernel<true>, grid, dim3(256), 0, s, W, CI, in, (const float *)nullptr, M, K, (int)N, out);

@@ -10,7 +10,7 @@
 //     3 001 words: neither K nor N a multiple of anything);
 //   * the relation head's per-head value projection U (models/transformer_captioner.py:319-326, first Linear) and the token
 //     projection of the d_model = 512 stress configuration.
-// Organisation (the row-panel kernel of the Transformer projections, csrc/sa_mlp.hip: linear_rows_kernel, made shape-agnostic):
+// Organisation (the row-panel kernel of the Transformer projections, csrc/linear_rows.hip: linear_rows_kernel, made shape-agnostic):
 // one (16 MT rows) x 64 column tile per workgroup, each wave 16 columns; K in chunks of 128: the activations of a chunk in LDS,
 // that chunk's weights in registers (through LDS for the transposed case); v_mfma_f32_16x16x4_f32 (exact fp32 products).  Rows,
 // columns and the K tail are guarded (zero fill), every operand has its own row stride, vector loads are used where the
@@ -18,13 +18,11 @@
 // group * group_stride + (within + skip) * ld -- the caption head reads positions 1.. of every sequence without a slice copy.
 // Optional split over K (gridDim.z slices, partial results [z][R][ldo] summed by the caller in order).
 #include "common.hpp"
+#include "mfma.hpp"
 
 namespace {
 
-using f32x4 = float __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-__device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
+using namespace spacap::mfma;
 
 struct RowsArgs {
   const float *a;

@@ -9,10 +9,11 @@
 // hipGraph draws new masks every step).  Dropout semantics as torch.nn.Dropout: keep with probability 1 - p,
 // scale kept values by 1 / (1 - p).
 #include "common.hpp"
+#include "mfma.hpp"
 
 namespace {
 
-using f32x4 = float __attribute__((ext_vector_type(4)));
+using spacap::mfma::f32x4;
 
 struct DropSeed {
   unsigned lo, hi;

@@ -20,6 +20,7 @@
 //   N <= 81 920  : Morton-bucketed scene, whole buckets skipped when provably unaffected (fps_bucket.inc)
 //   larger       : reference-style streaming with temp in the workspace (fps_generic_kernel)
 #include "common.hpp"
+#include "mfma.hpp"
 
 #pragma clang fp contract(off)
 
@@ -266,7 +267,7 @@ __global__ __launch_bounds__(BLOCK) void fps_generic_kernel(const float *__restr
   }
 }
 
-using f32x4 = float __attribute__((ext_vector_type(4)));
+using spacap::mfma::f32x4;
 
 // Large scenes (8 192 < N <= 81 920): spatially bucketed kernel with exact pruning.
 #include "fps_bucket.inc"

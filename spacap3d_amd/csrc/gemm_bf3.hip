@@ -20,30 +20,16 @@
 // phases.  Workgroup -> tile mapping: the column tiles of one row tile run back to back ON THE SAME XCD (workgroups are dealt
 // round robin to the 8 XCDs), so an activation tile is fetched from HBM once and re-read from that XCD's L2.
 // Epilogues: bias + ReLU (forward); none (data gradient: the consumer masks).  The weight gradient runs on the Linear layers'
-// split-bf16 kernel (csrc/wgrad_bf3.inc); spacap_gemm_bf3_wgrad_slabs sizes its row slabs for the relation head.
+// split-bf16 kernel (csrc/linear_grad.hip); spacap_gemm_bf3_wgrad_slabs sizes its row slabs for the relation head.
 #include "common.hpp"
+#include "mfma.hpp"
 
 namespace {
 
-using f32x4 = float __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-#define MFMA_B(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
+using namespace spacap::mfma;
 
 constexpr int BM = 128, BN = 128, BK = 32, LDS_ROW = BK + 8;   // halfs per LDS row (80 bytes)
 constexpr int IMG = BM * LDS_ROW;                               // one bf16 image of a 128 x 32 tile
-
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-
-__device__ __forceinline__ void split4(f32x4 v, bf16x4 &p0, bf16x4 &p1, bf16x4 &p2) {
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const __bf16 h = (__bf16)v[u];
-    const float r = v[u] - (float)h;
-    const __bf16 m = (__bf16)r;
-    p0[u] = h, p1[u] = m, p2[u] = (__bf16)(r - (float)m);
-  }
-}
 
 // W f32 [N][K] (trans == 0) or [K][N] (trans != 0: the image is of W^T) at row stride ldw -> Wp bf16 [3][N][K]
 __global__ __launch_bounds__(256) void gemm_bf3_split_w_kernel(const float *__restrict__ W, long ldw, int N, int K, int trans,
@@ -52,6 +38,7 @@ __global__ __launch_bounds__(256) void gemm_bf3_split_w_kernel(const float *__re
   if (e >= (long)N * K) return;
   const int n = (int)(e / K), k = (int)(e % K);
   const float v = trans ? W[(size_t)k * ldw + n] : W[(size_t)n * ldw + k];
+  // (split3 of mfma.hpp, spelled out: each piece is stored as soon as it exists, and the instruction order follows the source)
   const __bf16 h = (__bf16)v;
   const float r = v - (float)h;
   const __bf16 m = (__bf16)r;
@@ -127,7 +114,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf3_kernel(const float *__restric
 #pragma unroll
       for (int p = 0; p < 3; ++p) b[p] = *reinterpret_cast<const bf16x8 *>(sB + p * IMG + (64 * wn + 16 * nt + l15) * LDS_ROW + 8 * lg);
       // the six piece products, smallest first; four independent accumulators between two dependent instructions
-      constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
+      // (q outermost: the four accumulators alternate; PA, PB: mfma.hpp)
 #pragma unroll
       for (int q = 0; q < 6; ++q)
 #pragma unroll
@@ -247,7 +234,6 @@ bool wide_tail_shape(int C) { return C >= 16 && C % 4 == 0 && C / 4 <= 256 && 25
 //                           db1                 += column sums of dz1              (per workgroup partial)
 // with dz1 = dhid1 * [hid1 > 0].  The attention map is read TRANSPOSED, Pt[b,j,h,i] = P[b,h,i,j] (one tiled transposition
 // per direction, 0.5 GB): a key column's [H x K] block is then contiguous instead of 16 384 four-byte reads at stride K.
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // out[((b K + j) H + h) K + i] = in[((b H + h) K + i) K + j]  (to_t != 0)   or the inverse (to_t == 0); 32 x 32 tiles through LDS
 __global__ __launch_bounds__(256) void rel_wide_transpose_kernel(const float *__restrict__ in, float *__restrict__ out, int H, int K, int to_t) {

@@ -12,10 +12,11 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "mfma.hpp"
 
 namespace {
 
-using f32x4 = float __attribute__((ext_vector_type(4)));
+using spacap::mfma::f32x4;
 
 __device__ __forceinline__ bool better(float v, int i, float bv, int bi) {
   // candidate (v, i) replaces (bv, bi): larger value, NaN beats non-NaN, ties / NaN-NaN keep the lower index

@@ -26,11 +26,11 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "mfma.hpp"
 
 namespace {
 
-using f32x4 = float __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+using spacap::mfma::f32x4;
 
 struct MhaArgs {
   const float *q, *k, *v;

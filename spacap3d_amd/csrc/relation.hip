@@ -10,10 +10,11 @@
 // kernel reads dR once and produces both dP (reduction over d) and dV (reduction over the query index i) with
 // fixed summation order -- no atomics.
 #include "common.hpp"
+#include "mfma.hpp"
 
 namespace {
 
-using f32x4 = float __attribute__((ext_vector_type(4)));
+using spacap::mfma::f32x4;
 
 // grid (K, B): one workgroup writes the K x C slab of query i
 __global__ __launch_bounds__(256) void relation_fwd_kernel(const float *__restrict__ P, const float *__restrict__ V,

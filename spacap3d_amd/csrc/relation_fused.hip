@@ -24,14 +24,11 @@
 #include <atomic>
 
 #include "common.hpp"
+#include "mfma.hpp"
 
 namespace {
 
-using f32x4 = float __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-#define MFMA_B(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
+using namespace spacap::mfma;
 
 constexpr int H = 8, C = 128, NO = 9, LDT = C + 8, TI = 8, TJ = 8, TR = TI * TJ;   // 64 pair rows per tile
 constexpr int DPL = 12;                      // row stride of 9-wide tiles in LDS (9 values + 3 zeros: three k steps of 4)
@@ -39,8 +36,6 @@ constexpr int LDB = C + 8, IMG = TR * LDB;   // row-major bf16 piece [64 rows][1
 constexpr int LDR = TR + 8, IMGT = C * LDR;  // channel-major bf16 piece [128 channels][64 + 8]: 144-byte rows
 constexpr int PART = C * C + NO * C + C + C + 16;   // per-workgroup partial: dW2 | dW3 | db1 | db2 | db3 (padded)
 
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-__device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
 __device__ __forceinline__ f32x4 relu4(f32x4 v) { return f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)}; }
 
 // Tile rows are ordered key-major: row rr = jj * 8 + ii is the pair (query i0 + ii, key j0 + jj), so a 16-row matrix-core tile
@@ -49,28 +44,7 @@ __device__ __forceinline__ size_t pair_row(int b, int K, int i0, int j0, int rr)
 
 // ---- split-bf16 operands: x = x0 + x1 + x2 (three bf16 pieces, 24 mantissa bits), a product = the six piece products whose
 // weight is above 2^-24, each exact in the fp32 accumulator of v_mfma_f32_16x16x32_bf16: 6/16 of the fp32-MFMA time ----------
-__device__ __forceinline__ void split4(f32x4 v, bf16x4 &p0, bf16x4 &p1, bf16x4 &p2) {
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const __bf16 h = (__bf16)v[u];
-    const float r = v[u] - (float)h;
-    const __bf16 m = (__bf16)r;
-    p0[u] = h, p1[u] = m, p2[u] = (__bf16)(r - (float)m);
-  }
-}
-__device__ __forceinline__ void split8(f32x4 lo, f32x4 hi, bf16x8 *p) {
-  bf16x4 a[3], c[3];
-  split4(lo, a[0], a[1], a[2]);
-  split4(hi, c[0], c[1], c[2]);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) p[q] = bf16x8{a[q][0], a[q][1], a[q][2], a[q][3], c[q][0], c[q][1], c[q][2], c[q][3]};
-}
-__device__ __forceinline__ f32x4 mfma6(const bf16x8 *a, const bf16x8 *b, f32x4 acc) {   // smallest terms first
-  constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
-#pragma unroll
-  for (int q = 0; q < 6; ++q) acc = MFMA_B(a[PA[q]], b[PB[q]], acc);
-  return acc;
-}
+// (split4, split8, mfma6: mfma.hpp)
 __device__ __forceinline__ void st_pieces(__bf16 *dst, int piece_stride, f32x4 v) {   // 3 x 8 bytes
   bf16x4 p0, p1, p2;
   split4(v, p0, p1, p2);

@@ -1,5 +1,5 @@
-// Streaming split-bf16 ("bf16 x 3") shared-MLP kernels; included by sa_mlp.hip (uses its helpers: ld4, f32x4, split3,
-// MFMA_BF16, NPART).
+// Streaming split-bf16 ("bf16 x 3") shared-MLP kernels; included by sa_mlp.hip (uses its MFMA_BF16 and NPART, and
+// ld4, f32x4, split3 and the product order PA / PB of mfma.hpp).
 //
 // Layer:  z_out[r, :] = relu(bn(z_in[r, :])) W^T  + per-channel sum / sum of squares of z_out (pointnet2/pytorch_utils.py:
 // Conv2d -> BatchNorm2d -> ReLU chains built by SharedMLP, lib/pointnet2/pointnet2_modules.py:142-152).
@@ -254,13 +254,12 @@ __global__ __launch_bounds__(512) void sa_mid_fwd_bf3s_kernel(const float *__res
     for (int c = 0; c < NSTEP; ++c) {
       const int s = c / NG, g = c % NG;
       __builtin_amdgcn_sched_barrier(0);
-      // smallest terms first; the INTER accumulators alternate
-      constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PW[6] = {2, 0, 1, 1, 0, 0};
+      // smallest terms first (PA, PB: mfma.hpp); the INTER accumulators alternate
 #pragma unroll
       for (int p = 0; p < 6; ++p)
 #pragma unroll
         for (int i = 0; i < INTER; ++i)
-          acc[g * INTER + i] = MFMA_BF16(asp[PA[p]][s], wq[c & 1][i][PW[p]], acc[g * INTER + i]);
+          acc[g * INTER + i] = MFMA_BF16(asp[PA[p]][s], wq[c & 1][i][PB[p]], acc[g * INTER + i]);
       __builtin_amdgcn_sched_barrier(0);
       if (c + 2 < NSTEP) wload(c + 2);
     }

@@ -210,9 +210,8 @@ __global__ __launch_bounds__(512) void sa_dgrad_bf3s_kernel(const float *__restr
     for (int c = 0; c < NSTEP; ++c) {
       const int s = c / NCQ, cq = c % NCQ;
       __builtin_amdgcn_sched_barrier(0);
-      constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PW[6] = {2, 0, 1, 1, 0, 0};   // smallest terms first
 #pragma unroll
-      for (int p = 0; p < 6; ++p) acc[cq] = MFMA_BF16(asp[PA[p]][s], wq[c & 1][PW[p]], acc[cq]);
+      for (int p = 0; p < 6; ++p) acc[cq] = MFMA_BF16(asp[PA[p]][s], wq[c & 1][PB[p]], acc[cq]);   // smallest terms first (mfma.hpp)
       __builtin_amdgcn_sched_barrier(0);
       if (c + 2 < NSTEP) wload(c + 2);
     }

@@ -22,17 +22,22 @@
 // Weights stay in registers for the whole kernel (each wave owns 16*NT output channels); the activation tile
 // (64 rows) goes through LDS with a 4-word row padding, which makes the MFMA operand reads conflict-free.
 // All reductions (statistics, weight gradients) are two-stage with a fixed order: no float atomics.
+//
+// Two entry points that are not set abstraction live here because of the kernels they launch: spacap_gemm_rows_* (plain row
+// products on sa_mid_fwd_bf3s_kernel, one of the streaming kernels under the landing-register check of csrc/Makefile) and
+// spacap_rel_tail_fwd_f32 (the relation head's layers 2 and 3: the TAIL = true instantiation of sa_mid_fwd_kernel; its
+// backward is rel_tail.hip).  The process-wide launch state -- the reserved-CU counter, the cached CU count and the
+// SPACAP_SA_F32MFMA switch -- is defined here once and reached from other files through common.hpp.
 #include <hipcub/hipcub.hpp>
 
 #include <type_traits>
 
 #include "common.hpp"
+#include "mfma.hpp"
 #include <atomic>
 
 namespace {
-
-using f32x4 = float __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+using namespace spacap::mfma;
 
 constexpr int TM = 64;      // rows per tile of the forward / data-gradient GEMMs
 constexpr int TW = 32;      // rows per tile of the weight-gradient GEMM
@@ -40,9 +45,6 @@ constexpr int NPART = 1024; // partial-sum rows (= persistent workgroups) of eve
 
 // stats row of a layer: {mean, 1/sqrt(var+eps), gamma/sqrt(var+eps), beta}
 // coef  row of a layer (backward): {g, k0, k1, -}:  dz = g*dy + k0 - k1*z
-
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-__device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
 
 // r / d for row indices: a 64-bit division is ~200 instructions on this chip and the first-layer passes paid two of them per
 // row and thread; row counts fit 32 bits on the model's path (one 32-bit division, ~30 instructions), the general case stays
@@ -532,16 +534,9 @@ __global__ __launch_bounds__(256) void sa_mid_fwd_kernel(const float *__restrict
 // The kernels are in sa_bf3.inc (forward layers) and sa_bf3_dgrad.inc (data gradient).  Earlier variants of this layer (a
 // 32x32x2 fp32-MFMA kernel, an LDS-staged split-bf16 kernel, a streaming fp32 kernel, timing builds) are in the
 // history (round 2, `git log -- tools/lab/sa_variants`), not in the tree.
+// (split3 and the order of the six products: mfma.hpp; these kernels use the 32x32x16 form of the instruction)
 using f32x16 = float __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 #define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-__device__ __forceinline__ void split3(float v, __bf16 &h, __bf16 &m, __bf16 &l) {
-  h = (__bf16)v;
-  const float r = v - (float)h;
-  m = (__bf16)r;
-  l = (__bf16)(r - (float)m);
-}
 
 #include "sa_bf3.inc"
 #include "sa_bf3_dgrad.inc"
@@ -1324,7 +1319,8 @@ bool rows_layout(int B, int Np, long E, RowsLayout &L) {
 // when nothing runs beside it.
 // The library's one environment switch: SPACAP_SA_F32MFMA=1 keeps every shared-MLP product (forward layers, data gradient,
 // plain row products, pooling candidates from the epilogue) on the fp32-MFMA kernels instead of the split-bf16 streaming ones
-// -- the reference implementation the split kernels are gated against (tests/test_sa_gemm_kernels_gpu.py).
+// -- the reference implementation the split kernels are gated against (tests/test_sa_gemm_kernels_gpu.py).  Read HERE only:
+// the other files ask spacap::sa_f32_mfma_only() (common.hpp).
 inline bool f32_mfma_only() {
   static const bool on = getenv("SPACAP_SA_F32MFMA") != nullptr && atoi(getenv("SPACAP_SA_F32MFMA")) != 0;
   return on;
@@ -1638,6 +1634,7 @@ extern "C" int spacap_gemm_rows_f32(const float *x, const float *W, long R, int 
 }
 
 namespace spacap {
+bool sa_f32_mfma_only() { return f32_mfma_only(); }
 int sa_reserved_cus() { return reserved_cus(); }
 int device_cus() { return ::device_cus(); }
 }  // namespace spacap
@@ -2060,603 +2057,9 @@ extern "C" int spacap_sa_rows_scatter_f32(const float *dz, const int32_t *idx, i
   return rc ? rc : spacap_sa_rows_gather_f32(dz, B, Np, E, C, workspace, out, stream);
 }
 
-// ===========================================================================================================
-// Weight + bias gradient of a Linear layer:  dW[ck, cp] = sum_r g[r, ck] x[r, cp],  db[ck] = sum_r g[r, ck]
-// (torch.nn.Linear backward: models/transformer_captioner.py's projections and feed-forward layers).  The BLAS
-// path runs these [<= 2048 rows] x [128..2048]^2 reductions as a memset + a split-K GEMM + a separate column-sum
-// kernel (30 us of mostly latency for 67 MFLOP); here one launch produces per-slab partials of both (the bias
-// gradient falls out of the same staged tile as one more MFMA column against a constant 1), summed in slab order
-// by the caller.
-namespace {
-// (bx, gx): slab index / number of slabs; by, bz: 128-wide blocks of CK and CP
-template <bool WITH_BIAS>
-__device__ __forceinline__ void linear_wgrad_body(const float *__restrict__ g, const float *__restrict__ x, int CK, int CP,
-                                                  long R, float *__restrict__ part, int bx, int by, int bz, int gx) {
-  constexpr int CB = 128, LDG = CB + 16;
-  __shared__ __attribute__((aligned(16))) float s_g[TW * LDG];
-  __shared__ __attribute__((aligned(16))) float s_x[TW * LDG];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
-  const int ck0 = by * CB, cp0 = bz * CB;
-  const int c4 = tid & 31, r0 = tid >> 5;  // 32 float4 per 128-wide row, 8 rows per pass
-  f32x4 acc[2][8], accb[2];
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    accb[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int n = 0; n < 8; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  const long ntiles = (R + TW - 1) / TW;
-  // register pipeline: the next tile's rows are in flight while this tile's MFMAs run (a workgroup per CU has nobody
-  // else to hide the load latency behind)
-  f32x4 pa[TW / 8], pb[TW / 8];
-  auto fetch = [&](long t) {
-    const long row0 = t * TW;
-#pragma unroll
-    for (int i = 0; i < TW / 8; ++i) {
-      const int row = r0 + 8 * i;
-      pa[i] = pb[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (t < ntiles && row0 + row < R) {
-        pa[i] = ld4(g + (size_t)(row0 + row) * CK + ck0 + c4 * 4);
-        pb[i] = ld4(x + (size_t)(row0 + row) * CP + cp0 + c4 * 4);
-      }
-    }
-  };
-  fetch(bx);
-  for (long t = bx; t < ntiles; t += gx) {
-#pragma unroll
-    for (int i = 0; i < TW / 8; ++i) {
-      const int row = r0 + 8 * i;
-      st4(&s_g[row * LDG + c4 * 4], pa[i]);
-      st4(&s_x[row * LDG + c4 * 4], pb[i]);
-    }
-    __syncthreads();
-    fetch(t + gx);
-#pragma unroll
-    for (int ks = 0; ks < TW / 4; ++ks) {
-      float af[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) af[m] = s_g[(ks * 4 + lg) * LDG + (w * 2 + m) * 16 + l15];
-#pragma unroll
-      for (int n = 0; n < 8; ++n) {
-        const float b = s_x[(ks * 4 + lg) * LDG + n * 16 + l15];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) acc[m][n] = MFMA16(af[m], b, acc[m][n]);
-      }
-      if (WITH_BIAS) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m) accb[m] = MFMA16(af[m], 1.0f, accb[m]);
-      }
-    }
-    __syncthreads();
-  }
-  // partial layout per slab: [CK][CP] weights, then [CK] bias
-  float *o = part + (size_t)bx * ((size_t)CK * CP + (WITH_BIAS ? CK : 0));
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 8; ++n)
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        o[(size_t)(ck0 + (w * 2 + m) * 16 + 4 * lg + u) * CP + cp0 + n * 16 + l15] = acc[m][n][u];
-  if (WITH_BIAS && bz == 0 && l15 == 0) {
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) o[(size_t)CK * CP + ck0 + (w * 2 + m) * 16 + 4 * lg + u] = accb[m][u];
-  }
-}
-template <bool WITH_BIAS>
-__global__ __launch_bounds__(256) void linear_wgrad_kernel(const float *__restrict__ g, const float *__restrict__ x, int CK,
-                                                           int CP, long R, float *__restrict__ part) {
-  linear_wgrad_body<WITH_BIAS>(g, x, CK, CP, R, part, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x);
-}
-
-// Many weight gradients in ONE launch: the backward of a training step produces ~50 of them, most far too small to
-// fill the chip (the decoder's: 8 slabs x 1 - 16 blocks) and each a launch of its own; nothing but the optimizer
-// reads them, so they can all run together when the backward is over.  Job table by value in the kernel arguments
-// (hipGraph-capturable as it is); a workgroup finds its job by binary search over the first-block prefix.
-constexpr int WG_JOB_MAX = 72;
-struct WgradJob {
-  const float *g, *x;
-  float *part;
-  long R;
-  int CK, CP, gx, gy, with_bias, block0;
-};
-struct WgradTable {
-  int njobs, pad;
-  WgradJob job[WG_JOB_MAX];
-};
-#include "wgrad_bf3.inc"
-// (the split-bf16 body, wgrad_bf3.inc: the default; SPACAP_SA_F32MFMA=1 keeps the fp32-MFMA body)
-__global__ __launch_bounds__(256) void linear_wgrad_bf3_batched_kernel(const WgradTable T) {
-  int lo = 0, hi = T.njobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (T.job[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const WgradJob J = T.job[lo];
-  const int local = (int)blockIdx.x - J.block0;
-  const int bx = local % J.gx, by = (local / J.gx) % J.gy, bz = local / (J.gx * J.gy);
-  linear_wgrad_bf3_body(J.with_bias != 0, J.g, J.x, J.CK, J.CP, J.R, J.part, bx, by, bz, J.gx);
-}
-__global__ __launch_bounds__(256) void linear_wgrad_batched_kernel(const WgradTable T) {
-  int lo = 0, hi = T.njobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (T.job[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const WgradJob J = T.job[lo];
-  const int local = (int)blockIdx.x - J.block0;
-  const int bx = local % J.gx, by = (local / J.gx) % J.gy, bz = local / (J.gx * J.gy);
-  if (J.with_bias) linear_wgrad_body<true>(J.g, J.x, J.CK, J.CP, J.R, J.part, bx, by, bz, J.gx);
-  else linear_wgrad_body<false>(J.g, J.x, J.CK, J.CP, J.R, J.part, bx, by, bz, J.gx);
-}
-}  // namespace
-
-// number of row slabs (= partial results) for a (rows, CK, CP) problem; 0 when the shape has no kernel
-extern "C" int spacap_linear_wgrad_slabs(long R, int CK, int CP) {
-  if (R < 1 || CK < 128 || CP < 128 || CK % 128 || CP % 128) return 0;
-  const long tiles = (R + TW - 1) / TW, yz = (long)(CK / 128) * (CP / 128);
-  long n = 1024 / yz, cap = (4L << 20) / ((long)CK * CP);
-  if (n > cap) n = cap;
-  if (n > tiles) n = tiles;
-  return (int)(n < 1 ? 1 : n);
-}
-
-// part f32 [spacap_linear_wgrad_slabs(R,CK,CP)][CK*CP (+ CK when with_bias)]
-extern "C" int spacap_linear_wgrad_f32(const float *g, const float *x, long R, int CK, int CP, int with_bias, float *part,
-                                       spacap_stream_t stream) {
-  const char *what = "spacap_linear_wgrad_f32";
-  const int nslab = spacap_linear_wgrad_slabs(R, CK, CP);
-  SPACAP_REQUIRE(nslab > 0, "%s: (R=%ld, CK=%d, CP=%d) unsupported", what, R, CK, CP);
-  SPACAP_REQUIRE(g && x && part, "%s: null pointer", what);
-  hipStream_t s = spacap::as_stream(stream);
-  const dim3 grid(nslab, CK / 128, CP / 128);
-  if (!f32_mfma_only()) {
-    if (with_bias) hipLaunchKernelGGL((linear_wgrad_bf3_kernel<true>), grid, dim3(256), 0, s, g, x, CK, CP, R, part);
-    else hipLaunchKernelGGL((linear_wgrad_bf3_kernel<false>), grid, dim3(256), 0, s, g, x, CK, CP, R, part);
-  } else if (with_bias) hipLaunchKernelGGL((linear_wgrad_kernel<true>), grid, dim3(256), 0, s, g, x, CK, CP, R, part);
-  else hipLaunchKernelGGL((linear_wgrad_kernel<false>), grid, dim3(256), 0, s, g, x, CK, CP, R, part);
-  SPACAP_CHECK_LAUNCH(what);
-  return SPACAP_OK;
-}
-
-// The same with the number of row slabs chosen by the caller (1 <= nslab <= row tiles): part f32 [nslab][CK*CP (+ CK)].  For the
-// wide relation head of the stress configuration (4.2 M pair rows x 512 x 512): 64 slabs fill the chip twice over, where
-// spacap_linear_wgrad_slabs' 4 M-element cap on a partial set would leave it 16.
-extern "C" int spacap_linear_wgrad_nslab_f32(const float *g, const float *x, long R, int CK, int CP, int with_bias, int nslab, float *part,
-                                             spacap_stream_t stream) {
-  const char *what = "spacap_linear_wgrad_nslab_f32";
-  SPACAP_REQUIRE(spacap_linear_wgrad_slabs(R, CK, CP) > 0 && nslab >= 1 && nslab <= 65535 && nslab <= (R + TW - 1) / TW,
-                 "%s: (R=%ld, CK=%d, CP=%d, nslab=%d) unsupported", what, R, CK, CP, nslab);
-  SPACAP_REQUIRE(g && x && part, "%s: null pointer", what);
-  hipStream_t s = spacap::as_stream(stream);
-  const dim3 grid(nslab, CK / 128, CP / 128);
-  if (!f32_mfma_only()) {
-    if (with_bias) hipLaunchKernelGGL((linear_wgrad_bf3_kernel<true>), grid, dim3(256), 0, s, g, x, CK, CP, R, part);
-    else hipLaunchKernelGGL((linear_wgrad_bf3_kernel<false>), grid, dim3(256), 0, s, g, x, CK, CP, R, part);
-  } else if (with_bias) hipLaunchKernelGGL((linear_wgrad_kernel<true>), grid, dim3(256), 0, s, g, x, CK, CP, R, part);
-  else hipLaunchKernelGGL((linear_wgrad_kernel<false>), grid, dim3(256), 0, s, g, x, CK, CP, R, part);
-  SPACAP_CHECK_LAUNCH(what);
-  return SPACAP_OK;
-}
-
-// njobs independent weight gradients in one launch (same values as njobs calls of spacap_linear_wgrad_f32 with the
-// same arguments when nslabs[i] = spacap_linear_wgrad_slabs(...); any other slab count only changes how the rows are
-// grouped).  All arrays are HOST arrays, read before the call returns; part[i] holds nslabs[i] partial results.
-// slabs per job when many jobs share one launch: the batch fills the chip, so a workgroup can take 8 row tiles
-// (fewer partial results to write and to add up; one slab = the result itself for the decoder's 256 rows)
-extern "C" int spacap_linear_wgrad_slabs_batched(long R, int CK, int CP) {
-  const int single = spacap_linear_wgrad_slabs(R, CK, CP);
-  if (single == 0) return 0;
-  const long tiles = (R + TW - 1) / TW;
-  long n = tiles / 8;
-  if (n < 1) n = 1;
-  return (int)(n < single ? n : single);
-}
-
-extern "C" int spacap_linear_wgrad_batched_f32(const float *const *g, const float *const *x, const long *R, const int *CK,
-                                               const int *CP, const int *with_bias, const int *nslabs, float *const *part,
-                                               int njobs, spacap_stream_t stream) {
-  const char *what = "spacap_linear_wgrad_batched_f32";
-  SPACAP_REQUIRE(njobs >= 0 && (njobs == 0 || (g && x && R && CK && CP && with_bias && nslabs && part)), "%s: bad arguments",
-                 what);
-  hipStream_t s = spacap::as_stream(stream);
-  int i = 0;
-  while (i < njobs) {
-    WgradTable T;
-    T.njobs = 0, T.pad = 0;
-    long blocks = 0;
-    for (; i < njobs && T.njobs < WG_JOB_MAX; ++i) {
-      const int nslab = nslabs[i];
-      SPACAP_REQUIRE(spacap_linear_wgrad_slabs(R[i], CK[i], CP[i]) > 0 && nslab >= 1 && g[i] && x[i] && part[i],
-                     "%s: job %d: (R=%ld, CK=%d, CP=%d, slabs=%d) unsupported or null pointer", what, i, R[i], CK[i], CP[i], nslab);
-      WgradJob &J = T.job[T.njobs++];
-      J.g = g[i], J.x = x[i], J.part = part[i], J.R = R[i], J.CK = CK[i], J.CP = CP[i];
-      J.gx = nslab, J.gy = CK[i] / 128, J.with_bias = with_bias[i], J.block0 = (int)blocks;
-      blocks += (long)nslab * (CK[i] / 128) * (CP[i] / 128);
-      SPACAP_REQUIRE(blocks < 2147483647L, "%s: too many blocks", what);
-    }
-    if (!f32_mfma_only()) hipLaunchKernelGGL(linear_wgrad_bf3_batched_kernel, dim3((unsigned)blocks), dim3(256), 0, s, T);
-    else hipLaunchKernelGGL(linear_wgrad_batched_kernel, dim3((unsigned)blocks), dim3(256), 0, s, T);
-  }
-  SPACAP_CHECK_LAUNCH(what);
-  return SPACAP_OK;
-}
-
-// ===========================================================================================================
-// Weight gradient of a 1x1 convolution on CHANNEL-MAJOR tensors (the vote net and the feature-propagation MLPs:
-// models/voting_module.py:33-60, lib/pointnet2/pointnet2_modules.py:376-421; Conv1d/Conv2d k = 1 on (B, C, N)):
-//   dW[co, ci] = sum_b sum_n g[b, co, n] x[b, ci, n]
-// The convolution library runs this as an implicit-GEMM weight-gradient kernel (46 - 60 us for 256 x 256 over
-// 8 x 1 024 points) or as one small GEMM per scene; here both operands are read as [channel][32 points] panels
-// (contiguous along n), each (scene, point range) slab accumulates a 128 x 128 block by MFMA and writes a partial
-// result; the caller adds the slabs in order (spacap_sum_slabs_f32).
-namespace {
-// with_bias: the partial row is [CO * CI | CO rounded up to 4] and its tail receives db[co] = sum over the slab's points of g
-// (a column of ones beside x; written by the workgroups of the first input-channel block)
-__device__ __forceinline__ void conv1x1_wgrad_body(const float *__restrict__ g, const float *__restrict__ x, int CO, int CI,
-                                                   int N, int nsplit, float *__restrict__ part, int bx, int by, int bz,
-                                                   int with_bias = 0) {
-  constexpr int CB = 128, KT = 32, LDK = KT + 4;
-  __shared__ __attribute__((aligned(16))) float s_g[CB * LDK];
-  __shared__ __attribute__((aligned(16))) float s_x[CB * LDK];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
-  const int b = bx / nsplit, sl = bx % nsplit;
-  const int co0 = by * CB, ci0 = bz * CB;
-  const int tiles = N / KT, t_begin = (int)((long)tiles * sl / nsplit), t_end = (int)((long)tiles * (sl + 1) / nsplit);
-  const float *gb = g + ((size_t)b * CO + co0) * N, *xb = x + ((size_t)b * CI + ci0) * N;
-  const int k4 = tid & 7, c0 = tid >> 3;   // 8 float4 per 32-point row, 32 channels per pass
-  f32x4 acc[2][8];
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 8; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 accb[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-  const bool wb = with_bias && bz == 0;
-  for (int t = t_begin; t < t_end; ++t) {
-    const int n0 = t * KT;
-#pragma unroll
-    for (int i = 0; i < CB / 32; ++i) {
-      const int c = c0 + 32 * i;   // (channels past the end re-read the last one: their products are never stored)
-      st4(&s_g[c * LDK + k4 * 4], ld4(gb + (size_t)min(c, CO - 1 - co0) * N + n0 + k4 * 4));
-      st4(&s_x[c * LDK + k4 * 4], ld4(xb + (size_t)min(c, CI - 1 - ci0) * N + n0 + k4 * 4));
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < KT / 4; ++ks) {
-      float af[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) af[m] = s_g[((w * 2 + m) * 16 + l15) * LDK + ks * 4 + lg];
-#pragma unroll
-      for (int n = 0; n < 8; ++n) {
-        const float bb = s_x[(n * 16 + l15) * LDK + ks * 4 + lg];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) acc[m][n] = MFMA16(af[m], bb, acc[m][n]);
-      }
-      if (wb) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m) accb[m] = MFMA16(af[m], 1.0f, accb[m]);
-      }
-    }
-    __syncthreads();
-  }
-  float *o = part + (size_t)bx * ((size_t)CO * CI + (with_bias ? (size_t)((CO + 3) & ~3) : 0));
-  if (wb && l15 == 0) {
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int row = co0 + (w * 2 + m) * 16 + 4 * lg + u;
-        if (row < ((CO + 3) & ~3)) o[(size_t)CO * CI + row] = row < CO ? accb[m][u] : 0.f;
-      }
-  }
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 8; ++n)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int row = co0 + (w * 2 + m) * 16 + 4 * lg + u, col = ci0 + n * 16 + l15;
-        if (row < CO && col < CI) o[(size_t)row * CI + col] = acc[m][n][u];
-      }
-}
-
-__global__ __launch_bounds__(256) void conv1x1_wgrad_kernel(const float *__restrict__ g, const float *__restrict__ x, int CO,
-                                                            int CI, int N, int nsplit, float *__restrict__ part) {
-  conv1x1_wgrad_body(g, x, CO, CI, N, nsplit, part, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-
-// Several 1x1-convolution weight gradients in one launch (end of a backward pass: see linear_wgrad_batched_kernel)
-constexpr int CV_JOB_MAX = 64;
-struct ConvJob {
-  const float *g, *x;
-  float *part;
-  int CO, CI, N, nsplit, gx, gy, block0, with_bias;
-};
-struct ConvTable {
-  int njobs, pad;
-  ConvJob job[CV_JOB_MAX];
-};
-__global__ __launch_bounds__(256) void conv1x1_wgrad_batched_kernel(const ConvTable T) {
-  int lo = 0, hi = T.njobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (T.job[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const ConvJob J = T.job[lo];
-  const int local = (int)blockIdx.x - J.block0;
-  conv1x1_wgrad_body(J.g, J.x, J.CO, J.CI, J.N, J.nsplit, J.part, local % J.gx, (local / J.gx) % J.gy, local / (J.gx * J.gy),
-                     J.with_bias);
-}
-
-// (the split-bf16 bodies of wgrad_bf3.inc: the default; SPACAP_SA_F32MFMA=1 keeps the fp32-MFMA ones)
-__global__ __launch_bounds__(256) void conv1x1_wgrad_bf3_kernel(const float *__restrict__ g, const float *__restrict__ x, int CO,
-                                                                int CI, int N, int nsplit, float *__restrict__ part) {
-  conv1x1_wgrad_bf3_body(g, x, CO, CI, N, nsplit, part, blockIdx.x, blockIdx.y, blockIdx.z, 0);
-}
-__global__ __launch_bounds__(256) void conv1x1_wgrad_bf3_batched_kernel(const ConvTable T) {
-  int lo = 0, hi = T.njobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (T.job[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const ConvJob J = T.job[lo];
-  const int local = (int)blockIdx.x - J.block0;
-  conv1x1_wgrad_bf3_body(J.g, J.x, J.CO, J.CI, J.N, J.nsplit, J.part, local % J.gx, (local / J.gx) % J.gy, local / (J.gx * J.gy),
-                         J.with_bias);
-}
-
-inline int conv1x1_nsplit(int B, int CO, int CI, int N) {
-  const long yz = (long)((CO + 127) / 128) * ((CI + 127) / 128), tiles = N / 32;
-  long n = 512 / (yz * B), cap = (4L << 20) / ((long)CO * CI * B);
-  if (n > cap) n = cap;
-  if (n > tiles) n = tiles;
-  return (int)(n < 1 ? 1 : n);
-}
-}  // namespace
-
-// number of partial results (= B x point ranges) for a (B, CO, CI, N) problem; 0 when the shape has no kernel
-extern "C" int spacap_conv1x1_wgrad_slabs(int B, int CO, int CI, int N) {
-  if (B < 1 || N < 32 || N % 32 || CO < 1 || CI < 1) return 0;   // (any widths: 128 x 128 tiles with clamped tails)
-  return B * conv1x1_nsplit(B, CO, CI, N);
-}
-
-// slabs per job inside a batch (the batch fills the chip: ~16 point tiles per workgroup)
-extern "C" int spacap_conv1x1_wgrad_slabs_batched(int B, int CO, int CI, int N) {
-  if (spacap_conv1x1_wgrad_slabs(B, CO, CI, N) == 0) return 0;
-  // (512 points per workgroup: half the partial-sum traffic of 256 -- 65 instead of 130 MB per step at cfg2 -- and still ~1 000
-  // workgroups in the step's batch; 6.60 -> 6.57 ms same box, 1 024 points gives it back)
-  int nsplit = N / 512;
-  if (nsplit < 1) nsplit = 1;
-  const int single = conv1x1_nsplit(B, CO, CI, N);
-  return B * (nsplit < single ? nsplit : single);
-}
-
-// njobs independent 1x1-convolution weight gradients in one launch; all arrays are HOST arrays (read before the call
-// returns); part[i] receives nslabs[i] = B[i] x (point ranges) partial results (add in order).
-extern "C" int spacap_conv1x1_wgrad_batched_f32(const float *const *g, const float *const *x, const int *B, const int *CO,
-                                                const int *CI, const int *N, const int *nslabs, const int *with_bias,
-                                                float *const *part, int njobs, spacap_stream_t stream) {
-  const char *what = "spacap_conv1x1_wgrad_batched_f32";
-  SPACAP_REQUIRE(njobs >= 0 && (njobs == 0 || (g && x && B && CO && CI && N && nslabs && part)), "%s: bad arguments", what);
-  hipStream_t s = spacap::as_stream(stream);
-  int i = 0;
-  while (i < njobs) {
-    ConvTable T;
-    T.njobs = 0, T.pad = 0;
-    long blocks = 0;
-    for (; i < njobs && T.njobs < CV_JOB_MAX; ++i) {
-      SPACAP_REQUIRE(spacap_conv1x1_wgrad_slabs(B[i], CO[i], CI[i], N[i]) > 0 && nslabs[i] >= B[i] && nslabs[i] % B[i] == 0 &&
-                         g[i] && x[i] && part[i],
-                     "%s: job %d: (B=%d, CO=%d, CI=%d, N=%d, slabs=%d) unsupported or null pointer", what, i, B[i], CO[i], CI[i],
-                     N[i], nslabs[i]);
-      ConvJob &J = T.job[T.njobs++];
-      J.g = g[i], J.x = x[i], J.part = part[i], J.CO = CO[i], J.CI = CI[i], J.N = N[i];
-      J.nsplit = nslabs[i] / B[i], J.gx = nslabs[i], J.gy = (CO[i] + 127) / 128, J.block0 = (int)blocks, J.with_bias = with_bias ? with_bias[i] : 0;
-      blocks += (long)nslabs[i] * ((CO[i] + 127) / 128) * ((CI[i] + 127) / 128);
-      SPACAP_REQUIRE(blocks < 2147483647L, "%s: too many blocks", what);
-    }
-    if (!f32_mfma_only()) hipLaunchKernelGGL(conv1x1_wgrad_bf3_batched_kernel, dim3((unsigned)blocks), dim3(256), 0, s, T);
-    else hipLaunchKernelGGL(conv1x1_wgrad_batched_kernel, dim3((unsigned)blocks), dim3(256), 0, s, T);
-  }
-  SPACAP_CHECK_LAUNCH(what);
-  return SPACAP_OK;
-}
-
-// g f32 [B,CO,N], x f32 [B,CI,N] dense; part f32 [spacap_conv1x1_wgrad_slabs(B,CO,CI,N)][CO*CI]
-extern "C" int spacap_conv1x1_wgrad_f32(const float *g, const float *x, int B, int CO, int CI, int N, float *part,
-                                        spacap_stream_t stream) {
-  const char *what = "spacap_conv1x1_wgrad_f32";
-  const int nslab = spacap_conv1x1_wgrad_slabs(B, CO, CI, N);
-  SPACAP_REQUIRE(nslab > 0, "%s: (B=%d, CO=%d, CI=%d, N=%d) unsupported", what, B, CO, CI, N);
-  SPACAP_REQUIRE(g && x && part, "%s: null pointer", what);
-  if (!f32_mfma_only())
-    hipLaunchKernelGGL(conv1x1_wgrad_bf3_kernel, dim3(nslab, (CO + 127) / 128, (CI + 127) / 128), dim3(256), 0, spacap::as_stream(stream), g, x,
-                       CO, CI, N, nslab / B, part);
-  else
-    hipLaunchKernelGGL(conv1x1_wgrad_kernel, dim3(nslab, (CO + 127) / 128, (CI + 127) / 128), dim3(256), 0, spacap::as_stream(stream), g, x, CO, CI,
-                       N, nslab / B, part);
-  SPACAP_CHECK_LAUNCH(what);
-  return SPACAP_OK;
-}
-
-// ===========================================================================================================
-// Data gradient of the feed-forward block's second Linear fused with the backward of relu + dropout:
-//   dx[r, n] = (y[r, n] > 0) ? scale * sum_k g[r, k] W[k, n] : 0        g [R, 128], W [128, CP] (= w_2.weight), y [R, CP]
-// (models/transformer_captioner.py:117-126: w_2(dropout(relu(w_1 x))); y is the saved dropout(relu(.)) output, which is
-// positive exactly where the unit was active and kept).  The BLAS library runs this row-major x row-major product at
-// 28 TFLOP/s (37 us for 2048 x 2048 x 128) and the mask is one more pass over the 16 MB result.  Here: weights
-// stationary in registers (K = 128), one 64-row tile per workgroup and column block, accumulators transposed through
-// LDS so that y is read and dx written as full rows.
-namespace {
-__global__ __launch_bounds__(256) void linear_dgrad_mask_kernel(const float *__restrict__ g, const float *__restrict__ W,
-                                                                const float *__restrict__ y, float scale, long R, int CP,
-                                                                float *__restrict__ dx) {
-  constexpr int CK = 128, NT = 2, LD = CK + 4, KS = CK / 4, C4 = CK / 4, NV = TM * C4 / 256, RSTEP = 256 / C4;
-  constexpr int COB = 64 * NT, LDO = COB + 4, O4 = COB / 4, NO = TM * O4 / 256, OSTEP = 256 / O4;
-  __shared__ __attribute__((aligned(16))) float s_a[TM * LD];
-  __shared__ __attribute__((aligned(16))) float s_o[TM * LDO];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
-  const int cbb = blockIdx.y * COB, wc = w * 16 * NT, cb = cbb + wc;
-  const long row0 = (long)blockIdx.x * TM;
-  const int c4 = tid % C4, r0 = tid / C4, o4 = tid % O4, or0 = tid / O4;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int row = r0 + i * RSTEP;
-    f32x4 a = {0.f, 0.f, 0.f, 0.f};
-    if (row0 + row < R) a = ld4(g + (size_t)(row0 + row) * CK + c4 * 4);
-    st4(&s_a[row * LD + c4 * 4], a);
-  }
-  float wf[NT][KS];
-#pragma unroll
-  for (int j = 0; j < NT; ++j)
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) wf[j][ks] = W[(size_t)(ks * 4 + lg) * CP + cb + 16 * j + l15];
-  __syncthreads();
-  f32x4 acc[TM / 16][NT];
-#pragma unroll
-  for (int mt = 0; mt < TM / 16; ++mt)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[mt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-    for (int mt = 0; mt < TM / 16; ++mt) {
-      const float b = s_a[(mt * 16 + l15) * LD + ks * 4 + lg];
-#pragma unroll
-      for (int j = 0; j < NT; ++j) acc[mt][j] = MFMA16(wf[j][ks], b, acc[mt][j]);
-    }
-  }
-#pragma unroll
-  for (int mt = 0; mt < TM / 16; ++mt)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) st4(&s_o[(mt * 16 + l15) * LDO + wc + 16 * j + 4 * lg], acc[mt][j]);
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < NO; ++i) {
-    const int row = or0 + i * OSTEP;
-    if (row0 + row < R) {
-      const size_t o = (size_t)(row0 + row) * CP + cbb + o4 * 4;
-      const f32x4 d = ld4(&s_o[row * LDO + o4 * 4]), yv = ld4(y + o);
-      f32x4 r;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) r[u] = yv[u] > 0.f ? d[u] * scale : 0.f;
-      st4(dx + o, r);
-    }
-  }
-}
-}  // namespace
-
-// g f32 [R,128], W f32 [128,CP] (CP a multiple of 128), y f32 [R,CP], dx f32 [R,CP]; all dense
-extern "C" int spacap_linear_dgrad_mask_f32(const float *g, const float *W, const float *y, float scale, long R, int CK,
-                                            int CP, float *dx, spacap_stream_t stream) {
-  const char *what = "spacap_linear_dgrad_mask_f32";
-  SPACAP_REQUIRE(R >= 0 && CK == 128 && CP >= 128 && CP % 128 == 0, "%s: (R=%ld, CK=%d, CP=%d) unsupported", what, R, CK, CP);
-  if (R == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(g && W && y && dx, "%s: null pointer", what);
-  const long tiles = (R + TM - 1) / TM;
-  SPACAP_REQUIRE(tiles <= 2147483647L, "%s: too many rows", what);
-  hipLaunchKernelGGL(linear_dgrad_mask_kernel, dim3((unsigned)tiles, CP / 128), dim3(256), 0, spacap::as_stream(stream), g, W, y,
-                     scale, R, CP, dx);
-  SPACAP_CHECK_LAUNCH(what);
-  return SPACAP_OK;
-}
-
-// ===========================================================================================================
-// Relation head, layers 2 and 3 (models/transformer_captioner.py:319-326, 392-397) on R = B*K*K pair rows:
-//   hid2 = relu(hid1 W2^T + b2) [R,128],  pred = hid2 W3^T + b3 [R,NO3 = 9]
-// Forward: sa_mid_fwd_kernel<128, 2, TAIL> (one pass: read hid1, write hid2 and pred; the composition of a BLAS GEMM,
-// a ReLU pass and a second GEMM moves 5x the bytes).  Backward, first stage (this kernel): one streaming pass over
-// hid2 that produces dz2 = (dpred W3) * (hid2 > 0) and per-workgroup partial sums of dW3 = dpred^T hid2,
-// db2 = sum dz2 and db3 = sum dpred -- replacing a GEMM, a transposed GEMM, a masking pass and two column sums, each
-// a full pass over a 268 MB tensor.  dhid1 = dz2 W2 and dW2 = dz2^T hid1 stay BLAS GEMMs (MFMA-bound).
-namespace {
-constexpr int RT_NO = 9, RT_TM = 64;
-// part f32 [gridDim.x][RT_NO*128 + 128 + 16]: dW3 (row-major [9][128]), db2 [128], db3 [9 (+7 pad)]
-__global__ __launch_bounds__(256) void rel_tail_bwd_kernel(const float *__restrict__ dpred, const float *__restrict__ W3,
-                                                           const float *__restrict__ hid2, long R, float *__restrict__ dz2,
-                                                           float *__restrict__ part) {
-  constexpr int C = 128, PW = RT_NO * C + C + 16;
-  __shared__ __attribute__((aligned(16))) float s_dp[RT_TM * RT_NO];
-  __shared__ float s_red[8 * 32 * 41];
-  const int tid = threadIdx.x, c4 = tid & 31, r0 = tid >> 5;
-  float w3[RT_NO][4], aw[RT_NO][4], ab2[4] = {0.f, 0.f, 0.f, 0.f}, ab3[RT_NO];
-#pragma unroll
-  for (int o = 0; o < RT_NO; ++o) {
-    ab3[o] = 0.f;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) w3[o][u] = W3[o * C + c4 * 4 + u], aw[o][u] = 0.f;
-  }
-  const long ntiles = (R + RT_TM - 1) / RT_TM;
-  for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const long row0 = t * RT_TM;
-    __syncthreads();
-    for (int i = tid; i < RT_TM * RT_NO; i += 256) s_dp[i] = (row0 * RT_NO + i < R * RT_NO) ? dpred[row0 * RT_NO + i] : 0.f;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < RT_TM / 8; ++i) {
-      const int row = r0 + 8 * i;
-      if (row0 + row >= R) continue;
-      const f32x4 h = ld4(hid2 + (size_t)(row0 + row) * C + c4 * 4);
-      float d[RT_NO];
-#pragma unroll
-      for (int o = 0; o < RT_NO; ++o) d[o] = s_dp[row * RT_NO + o];
-      f32x4 dz = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int o = 0; o < RT_NO; ++o)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          dz[u] = fmaf(d[o], w3[o][u], dz[u]);
-          aw[o][u] = fmaf(d[o], h[u], aw[o][u]);
-        }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        dz[u] = h[u] > 0.f ? dz[u] : 0.f;
-        ab2[u] += dz[u];
-      }
-      st4(dz2 + (size_t)(row0 + row) * C + c4 * 4, dz);
-      if (c4 == 0) {
-#pragma unroll
-        for (int o = 0; o < RT_NO; ++o) ab3[o] += d[o];
-      }
-    }
-  }
-  // the 8 row groups of a column quad, added in a fixed order
-  __syncthreads();
-  float *mine = &s_red[(r0 * 32 + c4) * 41];
-#pragma unroll
-  for (int o = 0; o < RT_NO; ++o)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) mine[o * 4 + u] = aw[o][u];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) mine[36 + u] = ab2[u];
-  __syncthreads();
-  float *o_part = part + (size_t)blockIdx.x * PW;
-  for (int i = tid; i < 32 * 40; i += 256) {
-    const int q = i / 40, e = i % 40;
-    float a = 0.f;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) a += s_red[(g * 32 + q) * 41 + e];
-    if (e < 36) o_part[(e >> 2) * C + q * 4 + (e & 3)] = a;
-    else o_part[RT_NO * C + q * 4 + (e - 36)] = a;
-  }
-  __syncthreads();
-  if (c4 == 0) {
-#pragma unroll
-    for (int o = 0; o < RT_NO; ++o) s_red[r0 * 16 + o] = ab3[o];
-  }
-  __syncthreads();
-  if (tid < 16) {
-    float a = 0.f;
-    if (tid < RT_NO)
-#pragma unroll
-      for (int g = 0; g < 8; ++g) a += s_red[g * 16 + tid];
-    o_part[RT_NO * C + C + tid] = a;
-  }
-}
-}  // namespace
-
+// ---- relation head, layers 2 and 3, forward (backward: rel_tail.hip) -----------------------------------------------------------
+// hid2 = relu(hid1 W2^T + b2) [R,128],  pred = hid2 W3^T + b3 [R,9] on R = B*K*K pair rows in one pass of sa_mid_fwd_kernel's
+// TAIL = true form (read hid1, write hid2 and pred).  Its persistent grid leaves the reserved CUs out (fwd_resident).
 // hid1 f32 [R,128], W2 f32 [128,128], b2 f32 [128], W3 f32 [9,128], b3 f32 [9] -> hid2 f32 [R,128], pred f32 [R,9]
 extern "C" int spacap_rel_tail_fwd_f32(const float *hid1, const float *W2, const float *b2, const float *W3, const float *b3,
                                        long R, float *hid2, float *pred, spacap_stream_t stream) {
@@ -2667,120 +2070,7 @@ extern "C" int spacap_rel_tail_fwd_f32(const float *hid1, const float *W2, const
   static const int res = resident_blocks(sa_mid_fwd_kernel<128, 2, true>, lds);
   hipLaunchKernelGGL((sa_mid_fwd_kernel<128, 2, true>), dim3(grid_rows(fwd_resident(res), 1, tiles), 1), dim3(256), lds,
                      spacap::as_stream(stream), hid1, (const float *)nullptr, W2, 128, R, hid2, (double *)nullptr,
-                     TailArgs{b2, W3, b3, pred, RT_NO});
-  SPACAP_CHECK_LAUNCH(what);
-  return SPACAP_OK;
-}
-
-// number of partial rows the backward writes (each 9*128 + 128 + 16 floats)
-extern "C" int spacap_rel_tail_bwd_nparts(long R) {
-  const long tiles = (R + RT_TM - 1) / RT_TM;
-  return (int)(tiles < 1024 ? (tiles < 1 ? 1 : tiles) : 1024);
-}
-
-// dpred f32 [R,9], W3 f32 [9,128], hid2 f32 [R,128] -> dz2 f32 [R,128], part f32 [nparts][9*128 + 128 + 16]
-extern "C" int spacap_rel_tail_bwd_f32(const float *dpred, const float *W3, const float *hid2, long R, float *dz2, float *part,
-                                       spacap_stream_t stream) {
-  const char *what = "spacap_rel_tail_bwd_f32";
-  SPACAP_REQUIRE(dpred && W3 && hid2 && dz2 && part && R >= 1, "%s: bad arguments", what);
-  hipLaunchKernelGGL(rel_tail_bwd_kernel, dim3(spacap_rel_tail_bwd_nparts(R)), dim3(256), 0, spacap::as_stream(stream), dpred, W3,
-                     hid2, R, dz2, part);
-  SPACAP_CHECK_LAUNCH(what);
-  return SPACAP_OK;
-}
-
-// ===========================================================================================================
-// Row-panel products of the Transformer's d_model = 128 projections (models/transformer_captioner.py:63-99):
-//   out[r, n] = sum_k a[r, k] Wop[k, n] (+ bias[n])
-//   Wop[k, n] = TRANS_W ? W[n, k]  (forward  y = x W^T,  W [CO, K])
-//                       : W[k, n]  (data gradient dx = g W,  W [K, CO])
-// The BLAS library's heuristics pick one or two 128 x 256 macro tiles for these shapes when R is a few hundred rows
-// (the caption decoder: 8 x 32 tokens; 20 - 60 us per product on 1 - 3 workgroups).  Here: one (16 MT rows) x 64 column tile per workgroup, each wave 16 columns, the
-// activations of a 128-wide K chunk in LDS and that chunk's weights in registers, so a few-hundred-row product is tens
-// of workgroups of ~100 MFMA each (3 - 7 us).  Same summation order for every row: results do not depend on R.
-// a dense [R, K], K a multiple of 128.  (The vocabulary projection's gradients, 248 x 3 001, were tried in this
-// form too -- K-split partial sums for dx, a transposed loader for dW -- and lost to the BLAS kernels, 40 vs 35 us.)
-namespace {
-template <bool TRANS_W, int MT>
-__global__ __launch_bounds__(256) void linear_rows_kernel(const float *__restrict__ a, const float *__restrict__ W,
-                                                          const float *__restrict__ bias, long R, int K, int CO,
-                                                          float *__restrict__ out) {
-  constexpr int KC = 128, LD = KC + 4, KS = KC / 4, TMR = 16 * MT, C4 = KC / 4, RSTEP = 256 / C4, NV = TMR * C4 / 256;
-  __shared__ __attribute__((aligned(16))) float s_a[TMR * LD];
-  __shared__ __attribute__((aligned(16))) float s_w[TRANS_W ? 64 * LD : 4];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
-  const int cbb = blockIdx.y * 64, cb = cbb + w * 16;
-  const long row0 = (long)blockIdx.x * TMR;
-  const int c4 = tid % C4, r0 = tid / C4;
-  f32x4 acc[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int kc = 0; kc < K; kc += KC) {
-    if (kc) __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int row = r0 + i * RSTEP;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (row0 + row < R) v = ld4(a + (size_t)(row0 + row) * K + kc + c4 * 4);
-      st4(&s_a[row * LD + c4 * 4], v);
-    }
-    float wf[KS];
-    if (TRANS_W) {
-      // the 64 x 128 weight panel through LDS: full-row loads instead of 16-byte runs per lane
-#pragma unroll
-      for (int i = 0; i < 64 * C4 / 256; ++i) {
-        const int n = r0 + i * RSTEP;
-        st4(&s_w[n * LD + c4 * 4], ld4(W + (size_t)(cbb + n) * K + kc + c4 * 4));
-      }
-    } else {
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) wf[ks] = W[(size_t)(kc + ks * 4 + lg) * CO + cb + l15];
-    }
-    __syncthreads();
-    if (TRANS_W) {
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) wf[ks] = s_w[(w * 16 + l15) * LD + ks * 4 + lg];
-    }
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[mt] = MFMA16(wf[ks], s_a[(mt * 16 + l15) * LD + ks * 4 + lg], acc[mt]);
-  }
-  f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-  if (bias) bv = ld4(bias + cb + 4 * lg);
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const long row = row0 + mt * 16 + l15;
-    if (row < R) st4(out + (size_t)row * CO + cb + 4 * lg, acc[mt] + bv);
-  }
-}
-}  // namespace
-
-// 1 when (R, K, CO) has a dense row-panel kernel (spacap_linear_rows_f32)
-extern "C" int spacap_linear_rows_supported(long R, int K, int CO) {
-  return R >= 1 && K >= 128 && K <= 512 && K % 128 == 0 && CO >= 64 && CO % 64 == 0;
-}
-
-// a f32 [R,K], W f32 [CO,K] (trans_w) or [K,CO], bias f32 [CO] or null, out f32 [R,CO]; all dense, 16-byte aligned
-extern "C" int spacap_linear_rows_f32(const float *a, const float *W, const float *bias, long R, int K, int CO, int trans_w,
-                                      float *out, spacap_stream_t stream) {
-  const char *what = "spacap_linear_rows_f32";
-  SPACAP_REQUIRE(R >= 0 && K >= 128 && K <= 512 && K % 128 == 0 && CO >= 64 && CO % 64 == 0,
-                 "%s: (R=%ld, K=%d, CO=%d) unsupported", what, R, K, CO);
-  if (R == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(a && W && out, "%s: null pointer", what);
-  hipStream_t s = spacap::as_stream(stream);
-  const bool small = R <= 1024;
-  const long tiles = small ? (R + 31) / 32 : (R + 63) / 64;
-  SPACAP_REQUIRE(tiles <= 2147483647L, "%s: too many rows", what);
-  const dim3 grid((unsigned)tiles, CO / 64);
-  if (trans_w) {
-    if (small) hipLaunchKernelGGL((linear_rows_kernel<true, 2>), grid, dim3(256), 0, s, a, W, bias, R, K, CO, out);
-    else hipLaunchKernelGGL((linear_rows_kernel<true, 4>), grid, dim3(256), 0, s, a, W, bias, R, K, CO, out);
-  } else {
-    if (small) hipLaunchKernelGGL((linear_rows_kernel<false, 2>), grid, dim3(256), 0, s, a, W, bias, R, K, CO, out);
-    else hipLaunchKernelGGL((linear_rows_kernel<false, 4>), grid, dim3(256), 0, s, a, W, bias, R, K, CO, out);
-  }
+                     TailArgs{b2, W3, b3, pred, 9});
   SPACAP_CHECK_LAUNCH(what);
   return SPACAP_OK;
 }

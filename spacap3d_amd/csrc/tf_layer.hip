@@ -19,8 +19,8 @@
 //                         out2 = dy W2                  (optional GEMM, N2 = 128: through the output projection)
 //   tf_ffn1_kernel:       h = dropout(relu(n W_1^T + b_1))   [R, d_ff]   (weights stationary, 64 x 128 tiles)
 //
-// The feed-forward hidden layer's backward mask / data gradient is spacap_linear_dgrad_mask_f32 (sa_mlp.hip), the
-// weight gradients are the batched kernel of sa_mlp.hip (deferred to the end of the backward pass).
+// The feed-forward hidden layer's backward mask / data gradient is spacap_linear_dgrad_mask_f32 (linear_grad.hip), the
+// weight gradients are the batched kernel of linear_grad.hip (deferred to the end of the backward pass).
 //
 // Arithmetic: v_mfma_f32_16x16x4_f32 (fp32 in, fp32 accumulate: bit-for-bit an fp32 fma chain), computed transposed
 // (weights as the A operand) so that a lane ends up with consecutive columns of one row.  Operands reach the
@@ -29,21 +29,18 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "mfma.hpp"
 
 namespace {
 
-using f32x4 = float __attribute__((ext_vector_type(4)));
+using namespace spacap::mfma;
 using f32x2 = float __attribute__((ext_vector_type(2)));
-
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 constexpr int D = 128;        // d_model
 constexpr int BM = 16;        // rows per workgroup of the row kernel
 constexpr int LDT = D + 8;    // LDS row stride of a [rows][128] fp32 tile read with ds_read_b128 (conflict-free)
 
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
 __device__ __forceinline__ f32x2 ld2(const float *p) { return *reinterpret_cast<const f32x2 *>(p); }
-__device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
 
 // ---- dropout keep mask: the counter hash of elementwise.hip (seed word per call + device-resident step counter) ----
 struct DropSeed {
@@ -692,9 +689,6 @@ __global__ __launch_bounds__(256) void tf_ffn_kernel(const TfFfnArgs P) {
 // into matrix-core operand registers, one 32-deep contraction step ahead; the 64-row activation tile is split once into three
 // LDS images [64][128 + 8] which the hidden tile overwrites between the two products (everything of product 1 is in
 // accumulators by then).  52 KB of LDS, ~130 registers: three workgroups per CU.
-typedef __bf16 ff_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 ff_bf16x4 __attribute__((ext_vector_type(4)));
-#define FF_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 constexpr int FF_LD = D + 8, FF_IMG = 64 * FF_LD;
 struct TfFfnBf3Args {
   const float *x, *bias, *y;
@@ -707,15 +701,6 @@ struct TfFfnBf3Args {
   unsigned long long seed;
   const unsigned long long *seed_dev;
 };
-__device__ __forceinline__ void ff_split4(f32x4 v, ff_bf16x4 &p0, ff_bf16x4 &p1, ff_bf16x4 &p2) {
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const __bf16 h = (__bf16)v[u];
-    const float r = v[u] - (float)h;
-    const __bf16 m = (__bf16)r;
-    p0[u] = h, p1[u] = m, p2[u] = (__bf16)(r - (float)m);
-  }
-}
 template <bool BWD>
 __global__ __launch_bounds__(256, 3) void tf_ffn_bf3_kernel(const TfFfnBf3Args P) {
   __shared__ __attribute__((aligned(16))) __bf16 s_t[3 * FF_IMG];
@@ -745,43 +730,42 @@ __global__ __launch_bounds__(256, 3) void tf_ffn_bf3_kernel(const TfFfnBf3Args P
     for (int i = 0; i < 8; ++i) stg[i] = ld4(P.x + (size_t)min(row0 + r0 + 8 * i, P.R - 1) * D + c4 * 4);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      ff_bf16x4 p0, p1, p2;
-      ff_split4(stg[i], p0, p1, p2);
+      bf16x4 p0, p1, p2;
+      split4(stg[i], p0, p1, p2);
       __bf16 *d = s_t + (r0 + 8 * i) * FF_LD + 4 * c4;
-      *reinterpret_cast<ff_bf16x4 *>(d) = p0;
-      *reinterpret_cast<ff_bf16x4 *>(d + FF_IMG) = p1;
-      *reinterpret_cast<ff_bf16x4 *>(d + 2 * FF_IMG) = p2;
+      *reinterpret_cast<bf16x4 *>(d) = p0;
+      *reinterpret_cast<bf16x4 *>(d + FF_IMG) = p1;
+      *reinterpret_cast<bf16x4 *>(d + 2 * FF_IMG) = p2;
     }
   }
-  constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};   // smallest piece products first
   // weight operand of a product, step kc: wq[t][piece] = 8 consecutive contraction indices of output unit 32 w + 16 t + l15.  The
   // piece images are stored in OPERAND ORDER (tf_ffn_split_kernel): the 64 lanes of one load read 1 KB of consecutive bytes
   // (per-lane 16-byte reads at a row pitch of 256 B / 4 KB ran the kernel at the L1's line rate, not the matrix rate)
-  auto wload = [&](const __bf16 *base, size_t img, int kc, ff_bf16x8 (*wq)[3]) {
+  auto wload = [&](const __bf16 *base, size_t img, int kc, bf16x8 (*wq)[3]) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) wq[t][p] = *reinterpret_cast<const ff_bf16x8 *>(base + p * img + (size_t)(((t * 4 + kc) * 64 + lane) * 8));
+      for (int p = 0; p < 3; ++p) wq[t][p] = *reinterpret_cast<const bf16x8 *>(base + p * img + (size_t)(((t * 4 + kc) * 64 + lane) * 8));
   };
   // one product: acc[t][mt][u] = out[row 16 mt + l15][unit 32 w + 16 t + 4 lg + u] (weights as the A operand: a lane ends up with
   // four consecutive units of one row)
   auto product = [&](const __bf16 *wbase, size_t img, f32x4 (*acc)[4]) {
-    ff_bf16x8 wq[2][2][3];
+    bf16x8 wq[2][2][3];
     wload(wbase, img, 0, wq[0]);
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc) {
       if (kc + 1 < 4) wload(wbase, img, kc + 1, wq[(kc + 1) & 1]);
-      ff_bf16x8 a[4][3];
+      bf16x8 a[4][3];
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-        for (int p = 0; p < 3; ++p) a[mt][p] = *reinterpret_cast<const ff_bf16x8 *>(s_t + p * FF_IMG + (16 * mt + l15) * FF_LD + 32 * kc + 8 * lg);
+        for (int p = 0; p < 3; ++p) a[mt][p] = *reinterpret_cast<const bf16x8 *>(s_t + p * FF_IMG + (16 * mt + l15) * FF_LD + 32 * kc + 8 * lg);
 #pragma unroll
       for (int q = 0; q < 6; ++q)
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-          for (int mt = 0; mt < 4; ++mt) acc[t][mt] = FF_MFMA(wq[kc & 1][t][PA[q]], a[mt][PB[q]], acc[t][mt]);
+          for (int mt = 0; mt < 4; ++mt) acc[t][mt] = MFMA_B(wq[kc & 1][t][PA[q]], a[mt][PB[q]], acc[t][mt]);
     }
   };
   f32x4 acc[2][4];
@@ -819,12 +803,12 @@ __global__ __launch_bounds__(256, 3) void tf_ffn_bf3_kernel(const TfFfnBf3Args P
         }
       }
       if (valid && P.hid) st4(P.hid + (size_t)row * dff + c0 + e, o);
-      ff_bf16x4 p0, p1, p2;
-      ff_split4(o, p0, p1, p2);
+      bf16x4 p0, p1, p2;
+      split4(o, p0, p1, p2);
       __bf16 *d = s_t + (16 * mt + l15) * FF_LD + e;
-      *reinterpret_cast<ff_bf16x4 *>(d) = p0;
-      *reinterpret_cast<ff_bf16x4 *>(d + FF_IMG) = p1;
-      *reinterpret_cast<ff_bf16x4 *>(d + 2 * FF_IMG) = p2;
+      *reinterpret_cast<bf16x4 *>(d) = p0;
+      *reinterpret_cast<bf16x4 *>(d + FF_IMG) = p1;
+      *reinterpret_cast<bf16x4 *>(d + 2 * FF_IMG) = p2;
       acc[t][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
@@ -869,6 +853,7 @@ __global__ __launch_bounds__(256) void tf_ffn_split_kernel(const FfSplitTable T)
   __bf16 *o = T.out[layer];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
+    // (split3 of mfma.hpp, spelled out: each piece is stored as soon as it exists, and the instruction order follows the source)
     const __bf16 hh = (__bf16)v[i];
     const float r = v[i] - (float)hh;
     const __bf16 m = (__bf16)r;
@@ -1106,8 +1091,6 @@ extern "C" int spacap_decode_attn_f32(const float *qkv, float *kcache, float *vc
 // Arithmetic: split-bf16 (three bf16 pieces per operand, the six piece products above 2^-24 on v_mfma_f32_16x16x32_bf16:
 // fp32-equivalent logits at 6/16 of the fp32-MFMA time -- 1.6 GFLOP per word on the fp32 pipe alone is 10 us).  The weight's
 // pieces Wp bf16 [3][V][128] are made once per decoding call (spacap_gemm_bf3_split_w_f32).
-typedef __bf16 va_bf16x8 __attribute__((ext_vector_type(8)));
-#define VA_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 constexpr int VA_CHUNK = 64, VA_LDB = D + 8, VA_ROWS = 16;
 __global__ __launch_bounds__(256) void vocab_argmax_kernel(const float *__restrict__ x, const __bf16 *__restrict__ Wp, const float *__restrict__ bias,
                                                            long R, int V, int per_slice, float *__restrict__ best_v, int *__restrict__ best_i) {
@@ -1120,12 +1103,13 @@ __global__ __launch_bounds__(256) void vocab_argmax_kernel(const float *__restri
   const int ns = gridDim.y, sl = blockIdx.y;
   const int v_beg = sl * per_slice, v_end = min(V, v_beg + per_slice);
   // the sequences' rows as the A operand, split once: a[kc][piece] = pieces of x[row0 + l15][32 kc + 8 lg .. + 7]
-  va_bf16x8 a[D / 32][3];
+  bf16x8 a[D / 32][3];
   {
     const float *xr = x + (size_t)min(row0 + l15, R - 1) * D + 8 * lg;
 #pragma unroll
     for (int kc = 0; kc < D / 32; ++kc) {
       const f32x4 lo = ld4(xr + 32 * kc), hi = ld4(xr + 32 * kc + 4);
+      // (split8 of mfma.hpp, spelled out element by element: through the function this kernel's registers are allocated differently)
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float v = e < 4 ? lo[e] : hi[e - 4];
@@ -1141,14 +1125,14 @@ __global__ __launch_bounds__(256) void vocab_argmax_kernel(const float *__restri
   // staging: per piece 64 rows x 16 sixteen-byte pieces = 1 024 loads: 4 per thread and piece
   const int c8 = tid & 15, r0 = tid >> 4;
   const size_t wimg = (size_t)V * D;
-  va_bf16x8 stg[3][4];
+  bf16x8 stg[3][4];
   auto fetch = [&](int v0) {
 #pragma unroll
     for (int p = 0; p < 3; ++p)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int v = v0 + r0 + 16 * i;
-        stg[p][i] = *reinterpret_cast<const va_bf16x8 *>(Wp + p * wimg + (size_t)min(v, V - 1) * D + 8 * c8);
+        stg[p][i] = *reinterpret_cast<const bf16x8 *>(Wp + p * wimg + (size_t)min(v, V - 1) * D + 8 * c8);
       }
   };
   fetch(v_beg < V ? v_beg : 0);
@@ -1157,21 +1141,20 @@ __global__ __launch_bounds__(256) void vocab_argmax_kernel(const float *__restri
 #pragma unroll
     for (int p = 0; p < 3; ++p)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) *reinterpret_cast<va_bf16x8 *>(s_w + p * IMGW + (r0 + 16 * i) * VA_LDB + 8 * c8) = stg[p][i];
+      for (int i = 0; i < 4; ++i) *reinterpret_cast<bf16x8 *>(s_w + p * IMGW + (r0 + 16 * i) * VA_LDB + 8 * c8) = stg[p][i];
     __syncthreads();
     if (v0 + VA_CHUNK < v_end) fetch(v0 + VA_CHUNK);
     const int v = v0 + 16 * w + l15;                    // this lane's word of the chunk
     f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
-    constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
 #pragma unroll
     for (int kc = 0; kc < D / 32; ++kc) {
-      va_bf16x8 b[3];
+      bf16x8 b[3];
 #pragma unroll
-      for (int p = 0; p < 3; ++p) b[p] = *reinterpret_cast<const va_bf16x8 *>(s_w + p * IMGW + (16 * w + l15) * VA_LDB + 32 * kc + 8 * lg);
+      for (int p = 0; p < 3; ++p) b[p] = *reinterpret_cast<const bf16x8 *>(s_w + p * IMGW + (16 * w + l15) * VA_LDB + 32 * kc + 8 * lg);
 #pragma unroll
       for (int q = 0; q < 6; ++q) {
-        if (kc & 1) acc2 = VA_MFMA(a[kc][PA[q]], b[PB[q]], acc2);
-        else acc = VA_MFMA(a[kc][PA[q]], b[PB[q]], acc);
+        if (kc & 1) acc2 = MFMA_B(a[kc][PA[q]], b[PB[q]], acc2);
+        else acc = MFMA_B(a[kc][PA[q]], b[PB[q]], acc);
       }
     }
     if (v < v_end) {

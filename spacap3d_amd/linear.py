@@ -1,4 +1,4 @@
-"""y = x W^T + b with a one-launch weight + bias gradient (csrc/sa_mlp.hip: linear_wgrad_kernel).
+"""y = x W^T + b with a one-launch weight + bias gradient (csrc/linear_grad.hip: linear_wgrad_kernel).
 
 Counterpart of the ``nn.Linear`` projections / feed-forward layers of the reference Transformer
 (models/transformer_captioner.py:63-99, 117-126).  Forward and dX run on the row-panel kernel up to 512 rows (the default
@@ -15,7 +15,7 @@ from ._native import check, conv1x1_wgrad_partials, grad_slot, lib, linear_wgrad
 
 
 def rows_product(a2, W, bias, trans_w):
-    """out = a2 W^T (+ bias) when ``trans_w`` else a2 W, by the row-panel kernel (csrc/sa_mlp.hip: linear_rows_kernel);
+    """out = a2 W^T (+ bias) when ``trans_w`` else a2 W, by the row-panel kernel (csrc/linear_rows.hip: linear_rows_kernel);
     a2 (R, K) dense.  The caller checks ``use_rows``."""
     R, K = a2.shape
     CO = W.shape[0] if trans_w else W.shape[1]
@@ -131,7 +131,7 @@ def linear(x, weight, bias):
 class FFNTail(Function):
     """out = w_2(dropout(relu(h)))  (models/transformer_captioner.py:117-126, the part after w_1) as one autograd node:
     forward = the fused relu+dropout kernel + a BLAS GEMM; backward = one launch for d h (data gradient of w_2 with the
-    relu / dropout mask applied in its epilogue, csrc/sa_mlp.hip: linear_dgrad_mask_kernel) + the one-launch weight /
+    relu / dropout mask applied in its epilogue, csrc/linear_grad.hip: linear_dgrad_mask_kernel) + the one-launch weight /
     bias gradient."""
 
     @staticmethod
@@ -229,7 +229,7 @@ class Conv1x1(Function):
     """nn.Conv1d / nn.Conv2d with a 1x1 kernel on channel-major (B, C, N[, 1]) tensors -- the vote net and the
     feature-propagation MLPs (models/voting_module.py:33-60, lib/pointnet2/pointnet2_modules.py:376-421), the proposal head and the
     position embedding.  Forward (bias in the epilogue) and input gradient: csrc/conv1x1.hip (point counts that are not a
-    multiple of 64 fall back to the convolution library); weight gradient: csrc/sa_mlp.hip: conv1x1_wgrad_kernel + one sum
+    multiple of 64 fall back to the convolution library); weight gradient: csrc/conv1x1_wgrad.hip: conv1x1_wgrad_kernel + one sum
     over its slabs."""
 
     @staticmethod
@@ -323,7 +323,7 @@ class RelationTail(Function):
     (models/transformer_captioner.py:319-326, 392-397; hid1 = the first layer's ReLU output, 524 288 x 128 at the
     benchmark shape).  Forward: ONE kernel reads hid1 and writes hid2 and pred (csrc/sa_mlp.hip: sa_mid_fwd_kernel, TAIL).
     Backward: one streaming kernel gives dz2 = (dpred W3) * (hid2 > 0) and the partial sums of dW3, db2, db3
-    (rel_tail_bwd_kernel); dhid1 = dz2 W2 and dW2 = dz2^T hid1 are MFMA-bound BLAS GEMMs (the latter cut into 64 row
+    (csrc/rel_tail.hip: rel_tail_bwd_kernel); dhid1 = dz2 W2 and dW2 = dz2^T hid1 are MFMA-bound BLAS GEMMs (the latter cut into 64 row
     slabs: the BLAS heuristics do not split that reduction)."""
 
     SLABS = 64
@@ -488,7 +488,7 @@ class RelationWide(Function):
             nslab = int(lib.spacap_gemm_bf3_wgrad_slabs(R, C, C))
             pw = torch.empty(nslab, C * C, dtype=torch.float32, device=dev)
             # the Linear layers' split-bf16 weight-gradient kernel (row-major images read by transposing LDS reads:
-            # csrc/wgrad_bf3.inc)
+            # csrc/linear_grad.hip)
             check(lib.spacap_linear_wgrad_nslab_f32(dz2.data_ptr(), hid1.data_ptr(), R, C, C, 0, nslab, pw.data_ptr(), st),
                   "spacap_linear_wgrad_nslab_f32")
             dW2 = sum_slabs(pw, deferrable=True).view(C, C)

@@ -716,7 +716,7 @@ def test_no_library_gemm_or_convolution_kernel_inside_a_training_step(cfg, monke
     if cfg in ("cfg3", "cfg4"):
         assert any("dense_wgrad_tall_kernel" in n for n in names)
     if cfg == "cfg5":   # the 512-wide relation head and Linear layers: tiled split-bf16 products (csrc/gemm_bf3.hip)
-        # (the wide head's weight gradient: the Linear layers' split-bf16 kernel since round 6, csrc/wgrad_bf3.inc)
+        # (the wide head's weight gradient: the Linear layers' split-bf16 kernel since round 6, csrc/linear_grad.hip)
         assert any("gemm_bf3_kernel" in n for n in names) and any("linear_wgrad_bf3_kernel" in n for n in names)
         if not any("rel_wide_l1_bwd_kernel" in n for n in names) and os.environ.get("SPACAP_TEST_DUMP"):
             open(os.environ["SPACAP_TEST_DUMP"], "w").write("\n".join(sorted(names)))

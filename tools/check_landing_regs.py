@@ -1,4 +1,4 @@
-"""Build-time check for the streaming shared-MLP kernels (spacap3d_amd/csrc/sa_bf3.inc, sa_stream.inc).
+"""Build-time check for the streaming shared-MLP kernels (spacap3d_amd/csrc/sa_bf3.inc, sa_bf3_dgrad.inc).
 
 Their prefetched rows land in AGPRs through inline-asm loads; the C++ code sees them only after a hand-counted s_waitcnt whose
 "+a" operands name the same registers.  The register allocator knows the values are live in between, but nothing stops it from

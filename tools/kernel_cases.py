@@ -306,7 +306,7 @@ def sa_dgrad_wgrad_l1in(B, N, S, dev, label):
 
 
 def linear_wgrad(R, ck, cp, dev, label):
-    """torch.nn.Linear weight + bias gradient (csrc/wgrad_bf3.inc): split-bf16 products from transposing LDS reads."""
+    """torch.nn.Linear weight + bias gradient (csrc/linear_grad.hip): split-bf16 products from transposing LDS reads."""
     g, x = _rand(R, ck, dev=dev), _rand(R, cp, dev=dev)
     ns = int(lib.spacap_linear_wgrad_slabs(R, ck, cp))
     part = torch.empty(ns, ck * cp + ck, dtype=torch.float32, device=dev)
