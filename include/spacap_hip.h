@@ -931,6 +931,40 @@ int spacap_detection_nms_f32(const float *objectness, const int64_t *sem_cls, co
                              uint8_t *pred_mask, float *conf, uint8_t *valid, double *iou, uint8_t *good,
                              spacap_stream_t stream);
 
+/* ---- detection mAP / AR (replaces lib/ap_helper.py:195-250 APCalculator with utils/eval_det.py:21-52, 74-158;
+ * csrc/detection_ap.hip) ------------------------------------------------------------------------------------------------- */
+
+#define SPACAP_AP_EXISTS 0x80 /* flag byte of a record: bits 0..T-1 = true positive at threshold t, bit 7 = the record exists */
+
+/* Ground-truth matching of one batch for up to 4 IoU thresholds, one launch, one workgroup per (class, scene).
+ * bbox_corner f64 [B,K,8,3], valid u8 [B,K]; scores: conf f32 [B,K,NC] (per-class mode: every valid box is a prediction for
+ * every class) or, with conf NULL, obj_prob f32 [B,K] + sem_cls i64 [B,K] (a valid box is a prediction for its own class
+ * only).  gt_corner f64 [B,M,8,3] (f32 labels widened), sem_cls_label i64 [B,M], box_label_mask u8 [B,M] (only entries
+ * equal to 1 are ground truth; labels outside 0..NC-1 belong to no class), thresholds: T doubles ON THE HOST (read during the call).
+ * Writes, for each (scene, class), K records in [B,NC,K] slabs, every element on every call:
+ *   score f32   the records of the (scene, class) by score descending (compared as f32; equal scores lower proposal index
+ *               first, NaN last -- the reference's argsort leaves ties unspecified), then -inf for the unused tail;
+ *   flags u8    SPACAP_AP_EXISTS | bit t when the record is a TP at thresholds[t]: its best box (first strict maximum of
+ *               box3d_iou, utils/box_util.py:122-133, in f64 over the class's boxes in index order) has IoU > thresholds[t]
+ *               and no better-ranked record of the (scene, class) matched that box above the threshold; 0 in the tail;
+ *   index i16   the record's proposal (the tail lists the proposals without a record in index order);
+ * and ADDS the batch's number of ground-truth boxes per class into npos i32 [NC] (a plain read-modify-write ordered by the
+ * stream: clear it once before the first batch).  No global atomics, no state between calls.
+ * 1 <= K <= 512, 1 <= M <= 256, 1 <= NC <= 128, 1 <= T <= 4, 0 <= B <= 65535. */
+int spacap_detection_match_f32(const double *bbox_corner, const uint8_t *valid, const float *conf, const float *obj_prob,
+                               const int64_t *sem_cls, int B, int K, int NC, const double *gt_corner,
+                               const int64_t *sem_cls_label, const uint8_t *box_label_mask, int M, const double *thresholds,
+                               int T, float *score, uint8_t *flags, int16_t *index, int32_t *npos, spacap_stream_t stream);
+
+/* Precision / recall curve and VOC area (voc_ap with use_07_metric=False) per (class, threshold), one workgroup each,
+ * scanning the list in tiles.  flags u8 [NC,L]: per class the flag bytes of the whole run ordered by score descending, of
+ * which the first count[c] (i64 [NC], device) are records; npos i32 [NC] (device).  Writes ap f64 [NC,T], last_rec f64 [NC,T]
+ * (= rec[count-1]; 0 / (npos + 1e-8) for an empty class) and, unless rec and prec are both NULL, rec / prec f64 [NC,T,L]
+ * (the first count[c] of each row): rec = tp / (npos + 1e-8), prec = tp / max(tp + fp, DBL_EPSILON), bit-equal to numpy's.
+ * L >= 1, 1 <= NC <= 128, 1 <= T <= 4. */
+int spacap_ap_curve_f64(const uint8_t *flags, int64_t L, const int64_t *count, const int32_t *npos, int NC, int T, double *rec,
+                        double *prec, double *ap, double *last_rec, spacap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

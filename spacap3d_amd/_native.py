@@ -90,6 +90,8 @@ SIGNATURES = {
     "spacap_points_in_box_f32": (_i, [_p, _i, _i, _i, _p, _i, _p, ctypes.c_size_t, _p]),
     "spacap_detection_nms_f32": (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _i, _i, ctypes.c_double, _f,
                                       ctypes.c_double] + [_p] * 8 + [_p]),
+    "spacap_detection_match_f32": (_i, [_p] * 5 + [_i, _i, _i] + [_p] * 3 + [_i, _p, _i] + [_p] * 4 + [_p]),
+    "spacap_ap_curve_f64": (_i, [_p, ctypes.c_int64, _p, _p, _i, _i] + [_p] * 4 + [_p]),
     "spacap_stream_delay": (_i, [_i, _p]),
     "spacap_stream_wait_ge": (_i, [_p, _l, _i, _p, _p]),
     "spacap_stream_signal": (_i, [_p, _p, _p]),

@@ -734,11 +734,18 @@ class Evaluator:
 
     ``postprocess``: a POST_DICT-like mapping (scripts/eval.py:201-210; use_3d_nms only): each call then also runs
     ``postprocess.detection_postprocess`` on the forward's outputs, on the same stream, and stores its tensors under
-    ``post_obj_prob``, ``post_point_count``, ``post_nonempty_mask``, ``post_pred_mask``, ``post_valid`` and ``post_conf``."""
+    ``post_obj_prob``, ``post_point_count``, ``post_nonempty_mask``, ``post_pred_mask``, ``post_valid`` and ``post_conf``.
 
-    def __init__(self, model, graph=True, postprocess=None):
+    ``detection_ap``: a ``detection_ap.DetectionAP`` (needs ``postprocess``): each call then also runs its ``step`` on the
+    post-processing tensors and the batch's labels (``gt_box_corner_label``, ``sem_cls_label``, ``box_label_mask``), on the
+    same stream; read the metrics with ``detection_ap.compute_metrics()`` after the last batch."""
+
+    def __init__(self, model, graph=True, postprocess=None, detection_ap=None):
         self.model = model
         self.post_kw = None
+        if detection_ap is not None and postprocess is None:
+            raise ValueError("Evaluator: detection_ap needs postprocess")
+        self.detection_ap = detection_ap
         if postprocess is not None:
             from .postprocess import post_kwargs
             self.post_kw = post_kwargs(postprocess)
@@ -799,6 +806,9 @@ class Evaluator:
             for k, v in post.items():
                 if v is not None:
                     out["post_" + k] = v
+            if self.detection_ap is not None:
+                self.detection_ap.step(post, {k: (out[k] if k in out else d[k]) for k in (
+                    "bbox_corner", "sem_cls", "gt_box_corner_label", "sem_cls_label", "box_label_mask")})
         return out
 
 
