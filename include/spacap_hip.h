@@ -965,6 +965,42 @@ int spacap_detection_match_f32(const double *bbox_corner, const uint8_t *valid, 
 int spacap_ap_curve_f64(const uint8_t *flags, int64_t L, const int64_t *count, const int32_t *npos, int NC, int T, double *rec,
                         double *prec, double *ap, double *last_rec, spacap_stream_t stream);
 
+/* ---- caption metrics (replaces the candidate loop of lib/eval_helper.py:178-222 and the BLEU-4 / CIDEr-D / ROUGE-L scorers
+ * called at :304-317; csrc/caption_eval.hip).  Words are ids below 65 536; a sentence holds at most 64 tokens. ------------- */
+
+/* Candidate bookkeeping of one batch.  tokens i64 [B,K,L] (greedy decoding's words), nms_mask i64 [B,K], good_bbox_mask u8
+ * [B,K], dataset_idx i64 [B], scene_object_ids i64 [B,M], object_assignment i64 [B,K], key_table i32 [n_items, n_obj].
+ * Proposal (b,k) counts when nms_mask == 1, good_bbox_mask != 0 and its key row
+ *   key_table[dataset_idx[b]][scene_object_ids[b][object_assignment[b][k]]]
+ * is in 0..nkeys-1 (any index outside its table gives no row).  Its caption is decode_caption's: sos, the tokens up to and
+ * including the first eos, an eos appended when there was none (length <= L + 2).  Of all counting proposals of a key row the
+ * LAST in the order (call, scene, proposal) owns the row, as the reference's dict assignment does: cand_tok i32 [nkeys,64]
+ * (zero behind the caption) and cand_len i32 [nkeys] of that row are rewritten, every other row is left alone.
+ * State on the device, zeroed by the caller before the first batch of a run: stamp u64 [nkeys] (per row the 1-based number
+ * of its owner among all proposals seen so far; 0 = never written) and counter u64 [2] (the proposals seen so far; two cells
+ * so that no launch reads the one it writes).  Nothing depends on the host's view of earlier calls: a captured call replays
+ * correctly.  Two launches, global integer atomicMax on stamp only.
+ * 0 <= B <= 65535, 1 <= K <= 16384, L + 2 <= 64, 0 <= sos, eos <= 65535. */
+int spacap_caption_select_i32(const int64_t *tokens, const int64_t *nms_mask, const uint8_t *good_bbox_mask,
+                              const int64_t *dataset_idx, const int64_t *scene_object_ids, const int64_t *object_assignment,
+                              int B, int K, int L, int M, const int32_t *key_table, int n_items, int n_obj, int nkeys, int sos,
+                              int eos, uint64_t *stamp, uint64_t *counter, int32_t *cand_tok, int32_t *cand_len,
+                              spacap_stream_t stream);
+
+/* Per key row the parts of BLEU-4, ROUGE-L and CIDEr-D of its candidate against its references; one wave per row.
+ * References as CSR: ref_tok i32 [n_tok], ref_off / ref_len i32 [n_ref] (lengths <= 64), key_ref_off i32 [nkeys+1].
+ * Document frequencies: four tables, one per n-gram length n = 1..4, one after the other; table n is entries df_off[n-1] ..
+ * df_off[n] (df_off: 5 int64 ON THE HOST, read during the call) of df_code u64 (the n ids, 16 bits each, first word highest;
+ * ascending as unsigned) and df_idf f64 (log(nkeys) - log(max(1, df))); an n-gram absent from its table weighs log_nkeys.
+ * Writes bleu i32 [nkeys,10] = testlen, reflen (closest; ties to the shorter), guess[4], correct[4] (bleu_scorer.py:60-84),
+ * rouge f64 [nkeys] (rouge.py:45-75, beta = 1.2, bit-equal to the Python expression) and cider f64 [nkeys]
+ * (cider_scorer.py:106-181 with n = 4, sigma = 6, `length` = the number of bigrams as there; x 10 / references).
+ * nkeys = 0 is a no-op. */
+int spacap_caption_score_f64(const int32_t *cand_tok, const int32_t *cand_len, int nkeys, const int32_t *ref_tok, int64_t n_tok,
+                             const int32_t *ref_off, const int32_t *ref_len, int64_t n_ref, const int32_t *key_ref_off,
+                             const uint64_t *df_code, const double *df_idf, const int64_t *df_off, double log_nkeys,
+                             int32_t *bleu, double *rouge, double *cider, spacap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,9 @@ SIGNATURES = {
                                       ctypes.c_double] + [_p] * 8 + [_p]),
     "spacap_detection_match_f32": (_i, [_p] * 5 + [_i, _i, _i] + [_p] * 3 + [_i, _p, _i] + [_p] * 4 + [_p]),
     "spacap_ap_curve_f64": (_i, [_p, ctypes.c_int64, _p, _p, _i, _i] + [_p] * 4 + [_p]),
+    "spacap_caption_select_i32": (_i, [_p] * 6 + [_i] * 4 + [_p] + [_i] * 5 + [_p] * 4 + [_p]),
+    "spacap_caption_score_f64": (_i, [_p, _p, _i, _p, ctypes.c_int64, _p, _p, ctypes.c_int64, _p, _p, _p, _p,
+                                      ctypes.c_double, _p, _p, _p, _p]),
     "spacap_stream_delay": (_i, [_i, _p]),
     "spacap_stream_wait_ge": (_i, [_p, _l, _i, _p, _p]),
     "spacap_stream_signal": (_i, [_p, _p, _p]),

@@ -1,0 +1,353 @@
+// Caption metrics for gfx950 (MI355X): the candidate bookkeeping of the reference's feed_scene_cap (lib/eval_helper.py:
+// 178-222 with decode_caption, :46-57, and check_candidates, :59-69) and the per-object parts of BLEU-4, CIDEr-D and ROUGE-L
+// (lib/capeval/bleu/bleu_scorer.py:60-84, cider/cider_scorer.py:106-181, rouge/rouge.py:45-75) over word IDS: once a word is
+// an id (< 65 536) an n-gram is n x 16 bits in a u64 and nothing below is string processing.
+//
+//  1. caption_stamp_kernel + caption_write_kernel (spacap_caption_select_i32), per batch.  The reference assigns
+//     candidates[key] = [caption] in a loop over step, scene, proposal: the LAST write wins.  Pass one gives every counting
+//     proposal the stamp base + b*K + k + 1 (base = the proposals of all earlier calls, kept ON THE DEVICE so that a captured
+//     call replays with the right value) and takes the maximum per key row (global integer atomicMax: the result is the same
+//     for every schedule).  Pass two, one wave per proposal, lets only the holder of a row's stamp write the row: sos, the
+//     tokens up to and including the first eos, an eos appended when there was none; one lane per position, plain stores.
+//     The two cells of `counter` hand the base from call to call without a race: pass one reads [0] and writes [1] =
+//     base + B*K, pass two reads [1] and writes [0] = [1].
+//  2. caption_score_kernel (spacap_caption_score_f64), one wave per key row, one lane per token position, no state between
+//     keys.  The candidate and one reference at a time sit in LDS as four arrays of packed n-gram codes.  Per lane and n:
+//     whether the position is the first occurrence of its n-gram and how often the n-gram occurs (64 LDS compares), its idf
+//     by binary search in the sorted document-frequency table of that n (the only global reads inside the loop; absent =
+//     df 0 = log(NKEYS)).  BLEU's clipped counts, CIDEr's clipped tf-idf products and the norms are wave sums over the
+//     first-occurrence lanes; the longest common subsequence is the bit-parallel recurrence V' = (V + (V & M)) | (V & ~M)
+//     on one u64 (64 tokens are one word), M = the wave's ballot of "candidate token == this reference token".
+//
+// Arithmetic: -ffp-contract=off (Makefile default).  ROUGE-L is a chain of IEEE divisions, two multiplies and an add in the
+// reference's order: bit-equal to Python's.  CIDEr's sums run in wave-reduction order, not the reference's dict order.
+#include <math.h>
+
+#include "common.hpp"
+
+namespace {
+
+constexpr int CE_LMAX = 64;                         // tokens per sentence = lanes of a wave = bits of the LCS word
+constexpr double CE_BETA2 = 1.2 * 1.2;              // rouge.py: self.beta ** 2
+constexpr double CE_TWO_SIGMA2 = 2.0 * 6.0 * 6.0;   // cider_scorer.py: 2 * sigma ** 2
+
+struct SelectArgs {
+  const int64_t *tokens;             // [B,K,L]
+  const int64_t *nms_mask;           // [B,K]
+  const uint8_t *good;               // [B,K]
+  const int64_t *dataset_idx;        // [B]
+  const int64_t *scene_object_ids;   // [B,M]
+  const int64_t *object_assignment;  // [B,K]
+  const int32_t *key_table;          // [n_items, n_obj]
+  int B, K, L, M, n_items, n_obj, nkeys, sos, eos;
+  unsigned long long *stamp;         // [NKEYS]
+  unsigned long long *counter;       // [2]
+  int32_t *cand_tok;                 // [NKEYS, 64]
+  int32_t *cand_len;                 // [NKEYS]
+};
+
+// key row of proposal p = b*K + k when it counts, else -1
+__device__ __forceinline__ int caption_row(const SelectArgs &a, int b, int p) {
+  if (a.nms_mask[p] != 1 || a.good[p] == 0) return -1;
+  const int64_t item = a.dataset_idx[b], oa = a.object_assignment[p];
+  if (item < 0 || item >= a.n_items || oa < 0 || oa >= a.M) return -1;
+  const int64_t oid = a.scene_object_ids[(size_t)b * a.M + oa];
+  if (oid < 0 || oid >= a.n_obj) return -1;
+  const int row = a.key_table[(size_t)item * a.n_obj + oid];
+  return row >= 0 && row < a.nkeys ? row : -1;
+}
+
+__global__ __launch_bounds__(256) void caption_stamp_kernel(SelectArgs a) {
+  const int p = blockIdx.x * 256 + threadIdx.x, n = a.B * a.K;
+  const unsigned long long base = a.counter[0];
+  if (p == 0) a.counter[1] = base + (unsigned long long)n;
+  if (p >= n) return;
+  const int row = caption_row(a, p / a.K, p);
+  if (row >= 0) atomicMax(&a.stamp[row], base + (unsigned long long)p + 1ull);
+}
+
+__global__ __launch_bounds__(CE_LMAX) void caption_write_kernel(SelectArgs a) {
+  const int p = blockIdx.x, lane = threadIdx.x, n = a.B * a.K;
+  const unsigned long long next = a.counter[1];
+  if (p == 0 && lane == 0) a.counter[0] = next;                    // (nobody reads [0] in this pass)
+  const int row = caption_row(a, p / a.K, p);                      // uniform over the wave
+  if (row < 0 || a.stamp[row] != next - (unsigned long long)n + (unsigned long long)p + 1ull) return;
+  const int tok = lane < a.L ? (int)a.tokens[(size_t)p * a.L + lane] : 0;
+  const unsigned long long hit = __ballot(lane < a.L && tok == a.eos);
+  const int first = hit ? __ffsll((long long)hit) - 1 : -1;        // position of the first eos
+  const int body = first >= 0 ? first + 1 : a.L;                   // tokens kept (the eos included)
+  const int len = 1 + body + (first >= 0 ? 0 : 1);                 // <= L + 2 <= 64
+  int32_t *o = a.cand_tok + (size_t)row * CE_LMAX;
+  const int prev = __shfl(tok, lane > 0 ? lane - 1 : 0);           // token lane-1 sits at position lane
+  const int v = lane == 0 ? a.sos : (lane <= body ? prev : a.eos);
+  o[lane] = lane < len ? v : 0;
+  if (lane == 0) a.cand_len[row] = len;
+}
+
+// ---- scoring ---------------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+struct ScoreArgs {
+  const int32_t *cand_tok;      // [NKEYS, 64]
+  const int32_t *cand_len;      // [NKEYS]
+  const int32_t *ref_tok;       // CSR over the references
+  const int32_t *ref_off;       // [NREF]
+  const int32_t *ref_len;       // [NREF]
+  const int32_t *key_ref_off;   // [NKEYS + 1]
+  const uint64_t *df_code;      // the four sorted tables, one after the other
+  const double *df_idf;         // log(NKEYS) - log(max(1, df)) per entry
+  long long df_off[5];          // table n (n-grams of n words) = entries df_off[n-1] .. df_off[n]
+  long long n_tok, n_ref;
+  double log_nkeys;
+  int32_t *bleu;                // [NKEYS, 10]: testlen, reflen, guess[4], correct[4]
+  double *rouge;                // [NKEYS]
+  double *cider;                // [NKEYS]
+};
+
+// n-gram codes of the sentence in s_tok (len tokens) at this lane's position: code[n-1] is valid when lane + n <= len
+__device__ __forceinline__ void ngram_codes(const int *s_tok, int lane, uint64_t code[4]) {
+  uint64_t c = 0;
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int t = lane + n < CE_LMAX ? s_tok[lane + n] : 0;
+    c = (c << 16) | (uint64_t)(t & 0xFFFF);
+    code[n] = c;
+  }
+}
+
+__device__ __forceinline__ double idf_lookup(const ScoreArgs &a, int n, uint64_t code) {
+  long long lo = a.df_off[n], hi = a.df_off[n + 1];
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (a.df_code[mid] < code) lo = mid + 1;
+    else hi = mid;
+  }
+  return (lo < a.df_off[n + 1] && a.df_code[lo] == code) ? a.df_idf[lo] : a.log_nkeys;
+}
+
+__global__ __launch_bounds__(CE_LMAX) void caption_score_kernel(ScoreArgs a) {
+  __shared__ int s_tok[CE_LMAX];
+  __shared__ uint64_t s_cc[4][CE_LMAX];             // candidate n-gram codes
+  __shared__ uint64_t s_rc[4][CE_LMAX];             // reference n-gram codes
+  const int key = blockIdx.x, lane = threadIdx.x;
+  int lc = a.cand_len[key];
+  lc = lc < 0 ? 0 : (lc > CE_LMAX ? CE_LMAX : lc);
+  const int ctok = lane < lc ? a.cand_tok[(size_t)key * CE_LMAX + lane] : -1;
+  s_tok[lane] = ctok;
+  __syncthreads();
+  uint64_t cc[4];
+  ngram_codes(s_tok, lane, cc);
+#pragma unroll
+  for (int n = 0; n < 4; ++n) s_cc[n][lane] = cc[n];
+  __syncthreads();
+
+  // candidate: first occurrence, term frequency, tf-idf, norm per n
+  bool cfirst[4];
+  int ccount[4], maxref[4];
+  double cidf[4], cvec[4], cnorm[4], score[4];
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int valid = lc - n;                        // positions 0 .. valid-1 hold an (n+1)-gram
+    const bool in = lane < valid;
+    int cnt = 0, before = 0;
+    for (int j = 0; j < valid; ++j) {
+      const bool eq = s_cc[n][j] == cc[n];
+      cnt += eq ? 1 : 0;
+      before += (eq && j < lane) ? 1 : 0;
+    }
+    cfirst[n] = in && before == 0;
+    ccount[n] = cnt;
+    maxref[n] = 0;
+    cidf[n] = in ? idf_lookup(a, n, cc[n]) : 0.0;
+    cvec[n] = (double)cnt * cidf[n];
+    cnorm[n] = sqrt(wave_sum_f64(cfirst[n] ? cvec[n] * cvec[n] : 0.0));
+    score[n] = 0.0;
+  }
+  const int len_h = lc > 1 ? lc - 1 : 0;             // the reference's `length`: the number of BIGRAMS
+
+  long long r0 = a.key_ref_off[key], r1 = a.key_ref_off[key + 1];
+  r0 = r0 < 0 ? 0 : r0;
+  r1 = r1 > a.n_ref ? a.n_ref : r1;
+  int best_diff = 0x7fffffff, best_len = 0;
+  double pmax = 0.0, rmax = 0.0;
+  for (long long r = r0; r < r1; ++r) {              // (uniform over the wave)
+    int lr = a.ref_len[r];
+    lr = lr < 0 ? 0 : (lr > CE_LMAX ? CE_LMAX : lr);
+    const long long off = a.ref_off[r];
+    const bool ok = off >= 0 && off + lr <= a.n_tok;
+    __syncthreads();                                 // the previous reference's readers are done
+    s_tok[lane] = (ok && lane < lr) ? a.ref_tok[off + lane] : -2;
+    __syncthreads();
+    uint64_t rc[4];
+    ngram_codes(s_tok, lane, rc);
+#pragma unroll
+    for (int n = 0; n < 4; ++n) s_rc[n][lane] = rc[n];
+    __syncthreads();
+
+    // BLEU "closest" reference length: min over (|l - testlen|, l)
+    const int diff = lr > lc ? lr - lc : lc - lr;
+    if (diff < best_diff || (diff == best_diff && lr < best_len)) {
+      best_diff = diff;
+      best_len = lr;
+    }
+
+    // longest common subsequence, bit-parallel over the candidate's positions
+    uint64_t V = ~0ull;
+    for (int i = 0; i < lr; ++i) {
+      const int t = s_tok[i];
+      const uint64_t M = __ballot(lane < lc && ctok == t);
+      const uint64_t U = V & M;
+      V = (V + U) | (V & ~M);
+    }
+    const uint64_t low = lc >= 64 ? ~0ull : ((1ull << lc) - 1ull);
+    const int lcs = __popcll(~V & low);
+    const double prec = (double)lcs / (double)lc, rec = (double)lcs / (double)lr;
+    pmax = prec > pmax ? prec : pmax;
+    rmax = rec > rmax ? rec : rmax;
+
+    const int len_r = lr > 1 ? lr - 1 : 0;
+    const double delta = (double)(len_h - len_r);
+    const double penalty = exp(-(delta * delta) / CE_TWO_SIGMA2);
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      const int rvalid = lr - n;
+      // the reference's own vector: norm over its distinct n-grams
+      int rcnt = 0, rbefore = 0, cr = 0;
+      for (int j = 0; j < rvalid; ++j) {
+        const uint64_t x = s_rc[n][j];
+        const bool eq = x == rc[n];
+        rcnt += eq ? 1 : 0;
+        rbefore += (eq && j < lane) ? 1 : 0;
+        cr += x == cc[n] ? 1 : 0;                    // this lane's CANDIDATE n-gram in the reference
+      }
+      const bool rfirst = lane < rvalid && rbefore == 0;
+      double rv = 0.0;
+      if (rfirst) rv = (double)rcnt * idf_lookup(a, n, rc[n]);
+      const double rnorm = sqrt(wave_sum_f64(rfirst ? rv * rv : 0.0));
+      if (cfirst[n]) maxref[n] = cr > maxref[n] ? cr : maxref[n];
+      double term = 0.0;
+      if (cfirst[n]) {
+        const double vr = (double)cr * cidf[n];
+        term = (cvec[n] < vr ? cvec[n] : vr) * vr;
+      }
+      double val = wave_sum_f64(term);
+      if (cnorm[n] != 0.0 && rnorm != 0.0) val /= cnorm[n] * rnorm;
+      val *= penalty;
+      score[n] += val;
+    }
+  }
+
+  int correct[4];
+#pragma unroll
+  for (int n = 0; n < 4; ++n)
+    correct[n] = wave_sum_int(cfirst[n] ? (ccount[n] < maxref[n] ? ccount[n] : maxref[n]) : 0);
+  if (lane == 0) {
+    int32_t *o = a.bleu + (size_t)key * 10;
+    o[0] = lc;
+    o[1] = best_len;
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      o[2 + n] = lc - n > 0 ? lc - n : 0;
+      o[6 + n] = correct[n];
+    }
+    double rouge = 0.0;
+    if (pmax != 0.0 && rmax != 0.0) rouge = ((1.0 + CE_BETA2) * pmax * rmax) / (rmax + CE_BETA2 * pmax);
+    a.rouge[key] = rouge;
+    double avg = (((score[0] + score[1]) + score[2]) + score[3]) / 4.0;
+    const long long nref = r1 - r0;
+    if (nref > 0) avg /= (double)nref;
+    a.cider[key] = avg * 10.0;
+  }
+}
+
+}  // namespace
+
+extern "C" int spacap_caption_select_i32(const int64_t *tokens, const int64_t *nms_mask, const uint8_t *good_bbox_mask,
+                                         const int64_t *dataset_idx, const int64_t *scene_object_ids,
+                                         const int64_t *object_assignment, int B, int K, int L, int M, const int32_t *key_table,
+                                         int n_items, int n_obj, int nkeys, int sos, int eos, uint64_t *stamp, uint64_t *counter,
+                                         int32_t *cand_tok, int32_t *cand_len, spacap_stream_t stream) {
+  const char *what = "spacap_caption_select_i32";
+  SPACAP_REQUIRE(B >= 0 && B <= 65535 && K >= 1 && K <= 16384 && L >= 1 && L + 2 <= CE_LMAX && M >= 1 && n_items >= 1 && n_obj >= 1 &&
+                     nkeys >= 1,
+                 "%s: bad sizes (B=%d K=%d L=%d M=%d n_items=%d n_obj=%d nkeys=%d; L + 2 <= %d)", what, B, K, L, M, n_items,
+                 n_obj, nkeys, CE_LMAX);
+  SPACAP_REQUIRE(sos >= 0 && sos <= 65535 && eos >= 0 && eos <= 65535, "%s: bad sizes (sos=%d eos=%d: ids are 16 bits)", what, sos,
+                 eos);
+  if (B == 0) return SPACAP_OK;
+  SPACAP_REQUIRE(tokens && nms_mask && good_bbox_mask && dataset_idx && scene_object_ids && object_assignment && key_table && stamp &&
+                     counter && cand_tok && cand_len,
+                 "%s: null pointer", what);
+  SelectArgs a;
+  a.tokens = tokens;
+  a.nms_mask = nms_mask;
+  a.good = good_bbox_mask;
+  a.dataset_idx = dataset_idx;
+  a.scene_object_ids = scene_object_ids;
+  a.object_assignment = object_assignment;
+  a.key_table = key_table;
+  a.B = B;
+  a.K = K;
+  a.L = L;
+  a.M = M;
+  a.n_items = n_items;
+  a.n_obj = n_obj;
+  a.nkeys = nkeys;
+  a.sos = sos;
+  a.eos = eos;
+  a.stamp = reinterpret_cast<unsigned long long *>(stamp);
+  a.counter = reinterpret_cast<unsigned long long *>(counter);
+  a.cand_tok = cand_tok;
+  a.cand_len = cand_len;
+  const int n = B * K;
+  hipLaunchKernelGGL(caption_stamp_kernel, dim3((n + 255) / 256), dim3(256), 0, spacap::as_stream(stream), a);
+  SPACAP_CHECK_LAUNCH(what);
+  hipLaunchKernelGGL(caption_write_kernel, dim3(n), dim3(CE_LMAX), 0, spacap::as_stream(stream), a);
+  SPACAP_CHECK_LAUNCH(what);
+  return SPACAP_OK;
+}
+
+extern "C" int spacap_caption_score_f64(const int32_t *cand_tok, const int32_t *cand_len, int nkeys, const int32_t *ref_tok,
+                                        int64_t n_tok, const int32_t *ref_off, const int32_t *ref_len, int64_t n_ref,
+                                        const int32_t *key_ref_off, const uint64_t *df_code, const double *df_idf,
+                                        const int64_t *df_off, double log_nkeys, int32_t *bleu, double *rouge, double *cider,
+                                        spacap_stream_t stream) {
+  const char *what = "spacap_caption_score_f64";
+  SPACAP_REQUIRE(nkeys >= 0 && n_tok >= 0 && n_ref >= 0, "%s: bad sizes (nkeys=%d n_tok=%lld n_ref=%lld)", what, nkeys,
+                 (long long)n_tok, (long long)n_ref);
+  if (nkeys == 0) return SPACAP_OK;
+  SPACAP_REQUIRE(cand_tok && cand_len && ref_tok && ref_off && ref_len && key_ref_off && df_code && df_idf && df_off && bleu &&
+                     rouge && cider,
+                 "%s: null pointer", what);
+  SPACAP_REQUIRE(df_off[0] == 0 && df_off[0] <= df_off[1] && df_off[1] <= df_off[2] && df_off[2] <= df_off[3] && df_off[3] <= df_off[4],
+                 "%s: bad sizes (df_off must ascend from 0)", what);
+  ScoreArgs a;
+  a.cand_tok = cand_tok;
+  a.cand_len = cand_len;
+  a.ref_tok = ref_tok;
+  a.ref_off = ref_off;
+  a.ref_len = ref_len;
+  a.key_ref_off = key_ref_off;
+  a.df_code = df_code;
+  a.df_idf = df_idf;
+  for (int i = 0; i < 5; ++i) a.df_off[i] = df_off[i];
+  a.n_tok = n_tok;
+  a.n_ref = n_ref;
+  a.log_nkeys = log_nkeys;
+  a.bleu = bleu;
+  a.rouge = rouge;
+  a.cider = cider;
+  hipLaunchKernelGGL(caption_score_kernel, dim3(nkeys), dim3(CE_LMAX), 0, spacap::as_stream(stream), a);
+  SPACAP_CHECK_LAUNCH(what);
+  return SPACAP_OK;
+}

@@ -738,14 +738,23 @@ class Evaluator:
 
     ``detection_ap``: a ``detection_ap.DetectionAP`` (needs ``postprocess``): each call then also runs its ``step`` on the
     post-processing tensors and the batch's labels (``gt_box_corner_label``, ``sem_cls_label``, ``box_label_mask``), on the
-    same stream; read the metrics with ``detection_ap.compute_metrics()`` after the last batch."""
+    same stream; read the metrics with ``detection_ap.compute_metrics()`` after the last batch.
 
-    def __init__(self, model, graph=True, postprocess=None, detection_ap=None):
+    ``caption_eval``: a ``caption_eval.CaptionEval`` (needs ``postprocess``): each call then also runs its ``step`` (the
+    masks of ``postprocess.caption_eval_masks`` and the candidate bookkeeping) on the same stream.  The batch must be the dict
+    after ``get_scene_cap_loss(..., detection=True, caption=False)``: it carries ``object_assignment`` and ``bbox_mask`` next
+    to ``dataset_idx``, ``scene_object_ids`` and ``gt_box_corner_label``.  Read ``caption_eval.compute_metrics()`` after the
+    last batch."""
+
+    def __init__(self, model, graph=True, postprocess=None, detection_ap=None, caption_eval=None):
         self.model = model
         self.post_kw = None
         if detection_ap is not None and postprocess is None:
             raise ValueError("Evaluator: detection_ap needs postprocess")
+        if caption_eval is not None and postprocess is None:
+            raise ValueError("Evaluator: caption_eval needs postprocess")
         self.detection_ap = detection_ap
+        self.caption_eval = caption_eval
         if postprocess is not None:
             from .postprocess import post_kwargs
             self.post_kw = post_kwargs(postprocess)
@@ -809,6 +818,14 @@ class Evaluator:
             if self.detection_ap is not None:
                 self.detection_ap.step(post, {k: (out[k] if k in out else d[k]) for k in (
                     "bbox_corner", "sem_cls", "gt_box_corner_label", "sem_cls_label", "box_label_mask")})
+            if self.caption_eval is not None:
+                need = ("lang_cap", "point_clouds", "bbox_corner", "objectness_scores", "sem_cls", "gt_box_corner_label",
+                        "object_assignment", "bbox_mask", "scene_object_ids", "dataset_idx")
+                missing = [k for k in need if k not in out and k not in d]
+                if missing:
+                    raise KeyError(f"Evaluator: caption_eval needs {missing} in the batch or the forward's outputs: pass the "
+                                   "dict after get_scene_cap_loss(..., detection=True, caption=False)")
+                self.caption_eval.step({k: (out[k] if k in out else d[k]) for k in need}, **self.post_kw)
         return out
 
 
