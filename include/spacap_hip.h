@@ -1001,6 +1001,27 @@ int spacap_caption_score_f64(const int32_t *cand_tok, const int32_t *cand_len, i
                              const uint64_t *df_code, const double *df_idf, const int64_t *df_off, double log_nkeys,
                              int32_t *bleu, double *rouge, double *cider, spacap_stream_t stream);
 
+/* ---- dense-caption predictions (replaces the host loop a caller of the reference writes over parse_predictions with
+ * per_class_proposal=False, lib/ap_helper.py:145-158, and decode_caption, lib/eval_helper.py:46-57; csrc/predictions.hip) --- */
+
+/* The proposals of each scene that survive post-processing, ranked, with class, score, box and caption; one launch, one
+ * workgroup per scene, no ground truth.  valid u8 [B,K] (spacap_detection_nms_f32's: pred_mask & obj_prob > conf_thresh),
+ * obj_prob f32 [B,K], sem_cls i64 [B,K], bbox_corner f64 [B,K,8,3], tokens i64 [B,K,L] (greedy decoding's words).
+ * A proposal is kept exactly when valid != 0.  Order: obj_prob descending compared as f32, equal scores lower proposal index
+ * first (-0 == +0), NaN behind every number.  Writes, every element on every call:
+ *   count i32 [B]           the number of kept proposals of the scene;
+ *   index i32 [B,K]         the proposal at each rank, -1 behind count;
+ *   score f32 [B,K], cls i32 [B,K], corners f64 [B,K,8,3]   obj_prob, sem_cls and bbox_corner of that proposal (bit copies);
+ *   tokens i32 [B,K,L+2]    decode_caption's sentence: sos, the tokens through the first eos inclusive, an eos appended when
+ *                           there was none, then zeros;
+ *   length i32 [B,K]        its number of tokens, sos and eos included (2 .. L+2);
+ * rows behind count hold zeros.  No global atomics, no state between calls: a captured call replays correctly.
+ * bbox_corner and corners must be 16-byte aligned.  1 <= K <= 512, 1 <= L <= 62, 0 <= B <= 65535, sos, eos >= 0. */
+int spacap_dense_caption_select(const uint8_t *valid, const float *obj_prob, const int64_t *sem_cls, const double *bbox_corner,
+                                const int64_t *tokens, int B, int K, int L, int sos, int eos, int32_t *count, int32_t *index,
+                                float *score, int32_t *cls, double *corners, int32_t *out_tokens, int32_t *length,
+                                spacap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

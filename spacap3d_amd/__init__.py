@@ -9,6 +9,10 @@ Sub-modules
 ``pointnet2_modules``   PointnetSAModuleVotes, PointnetFPModule
 ``models``              backbone, voting, proposal, transformer captioner, SpaCapNet
 ``loss_helper``         get_scene_cap_loss (device-agnostic restatement)
+``postprocess``         evaluation post-processing on the device: empty boxes, class-aware 3D NMS, box IoU
+``detection_ap``        detection mAP / AR on the device
+``caption_eval``        caption metrics on the device: candidates, BLEU-4, CIDEr-D, ROUGE-L
+``predictions``         dense-caption predictions on the device: kept boxes, ranked, with class, score and caption
 ``synthetic``           seeded synthetic scenes / labels
 ``distributed``         one-process-per-GPU data parallelism (single flat gradient all-reduce over RCCL)
 

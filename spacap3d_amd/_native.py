@@ -95,6 +95,7 @@ SIGNATURES = {
     "spacap_caption_select_i32": (_i, [_p] * 6 + [_i] * 4 + [_p] + [_i] * 5 + [_p] * 4 + [_p]),
     "spacap_caption_score_f64": (_i, [_p, _p, _i, _p, ctypes.c_int64, _p, _p, ctypes.c_int64, _p, _p, _p, _p,
                                       ctypes.c_double, _p, _p, _p, _p]),
+    "spacap_dense_caption_select": (_i, [_p] * 5 + [_i] * 5 + [_p] * 7 + [_p]),
     "spacap_stream_delay": (_i, [_i, _p]),
     "spacap_stream_wait_ge": (_i, [_p, _l, _i, _p, _p]),
     "spacap_stream_signal": (_i, [_p, _p, _p]),

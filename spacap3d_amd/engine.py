@@ -744,11 +744,20 @@ class Evaluator:
     masks of ``postprocess.caption_eval_masks`` and the candidate bookkeeping) on the same stream.  The batch must be the dict
     after ``get_scene_cap_loss(..., detection=True, caption=False)``: it carries ``object_assignment`` and ``bbox_mask`` next
     to ``dataset_idx``, ``scene_object_ids`` and ``gt_box_corner_label``.  Read ``caption_eval.compute_metrics()`` after the
-    last batch."""
+    last batch.
 
-    def __init__(self, model, graph=True, postprocess=None, detection_ap=None, caption_eval=None):
+    ``predictions``: ``(sos, eos)``, the two word ids (needs ``postprocess``): each call then also runs
+    ``predictions.dense_caption_predictions`` on the post-processing tensors and the forward's boxes, classes and captions, on
+    the same stream, and stores its tensors under ``pred_count``, ``pred_index``, ``pred_score``, ``pred_cls``,
+    ``pred_corners``, ``pred_tokens`` and ``pred_length`` (``predictions.to_records`` turns them into lists).  The batch
+    needs no ground-truth key."""
+
+    def __init__(self, model, graph=True, postprocess=None, detection_ap=None, caption_eval=None, predictions=None):
         self.model = model
         self.post_kw = None
+        if predictions is not None and postprocess is None:
+            raise ValueError("Evaluator: predictions needs postprocess")
+        self.predictions = None if predictions is None else (int(predictions[0]), int(predictions[1]))
         if detection_ap is not None and postprocess is None:
             raise ValueError("Evaluator: detection_ap needs postprocess")
         if caption_eval is not None and postprocess is None:
@@ -826,6 +835,11 @@ class Evaluator:
                     raise KeyError(f"Evaluator: caption_eval needs {missing} in the batch or the forward's outputs: pass the "
                                    "dict after get_scene_cap_loss(..., detection=True, caption=False)")
                 self.caption_eval.step({k: (out[k] if k in out else d[k]) for k in need}, **self.post_kw)
+            if self.predictions is not None:
+                from .predictions import KEYS, dense_caption_predictions
+                pred = dense_caption_predictions(post, out, *self.predictions)
+                for k in KEYS:
+                    out["pred_" + k] = pred[k]
         return out
 
 
