@@ -20,16 +20,11 @@ import ctypes
 import numpy as np
 import torch
 
+from ._eval_util import gpu, mask_u8, word
 from ._native import check, lib
 
 LMAX = 64            # tokens per sentence (csrc/caption_eval.hip: one lane per token)
 MAX_IDS = 1 << 16    # an n-gram is n x 16 bits
-
-
-def _gpu(t, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"caption_eval: {name}: CPU not supported")
-    return t
 
 
 def ngram_tables(refs, key_of_ref, nkeys):
@@ -196,7 +191,7 @@ class CaptionEval:
     def set_candidates(self, tokens, lengths):
         """Replaces the run's candidate table: ``tokens`` int (NKEYS, <= 64) and ``lengths`` int (NKEYS,) device tensors in
         corpus order (captions decoded elsewhere); later ``step`` calls overwrite the rows they hit."""
-        tokens, lengths = _gpu(tokens, "tokens"), _gpu(lengths, "lengths")
+        tokens, lengths = gpu("caption_eval", tokens, "tokens"), gpu("caption_eval", lengths, "lengths")
         n = self.corpus.nkeys
         if tokens.dim() != 2 or tokens.shape[0] != n or tokens.shape[1] > LMAX or tuple(lengths.shape) != (n,):
             raise RuntimeError(f"caption_eval: candidates must be ({n}, <= {LMAX}) tokens and ({n},) lengths")
@@ -211,7 +206,7 @@ class CaptionEval:
         ``postprocess.caption_eval_masks`` (``nms_masks``, ``good_bbox_masks``); computed here from ``data_dict`` (with the
         ``detection_postprocess`` keyword arguments ``post``) when not given.  Two launches on the current stream, no host
         synchronisation; L + 2 <= 64."""
-        cap = _gpu(data_dict["lang_cap"], "lang_cap")
+        cap = gpu("caption_eval", data_dict["lang_cap"], "lang_cap")
         dev = cap.device
         if masks is None:
             from .postprocess import caption_eval_masks
@@ -223,11 +218,11 @@ class CaptionEval:
         B, K, L = cap.shape
         if L + 2 > LMAX:
             raise RuntimeError(f"caption_eval: L={L} tokens per caption, supported <= {LMAX - 2}")
-        idx = _gpu(data_dict["dataset_idx"], "dataset_idx").reshape(-1)
-        ids = _gpu(data_dict["scene_object_ids"], "scene_object_ids")
-        oa = _gpu(data_dict["object_assignment"], "object_assignment")
-        nms = _gpu(masks["nms_masks"], "nms_masks")
-        good = _gpu(masks["good_bbox_masks"], "good_bbox_masks")
+        idx = gpu("caption_eval", data_dict["dataset_idx"], "dataset_idx").reshape(-1)
+        ids = gpu("caption_eval", data_dict["scene_object_ids"], "scene_object_ids")
+        oa = gpu("caption_eval", data_dict["object_assignment"], "object_assignment")
+        nms = gpu("caption_eval", masks["nms_masks"], "nms_masks")
+        good = gpu("caption_eval", masks["good_bbox_masks"], "good_bbox_masks")
         if idx.numel() != B or ids.dim() != 2 or ids.shape[0] != B or tuple(oa.shape) != (B, K) or tuple(nms.shape) != (B, K) \
                 or tuple(good.shape) != (B, K):
             raise RuntimeError(f"caption_eval: expected dataset_idx (B,), scene_object_ids (B, M), object_assignment / masks "
@@ -239,7 +234,7 @@ class CaptionEval:
             raise RuntimeError(f"caption_eval: the run lives on {self.device}, got tensors on {dev}")
         c = self.corpus.on(dev)
         cap, idx, ids, oa, nms = (t.long().contiguous() for t in (cap, idx, ids, oa, nms))
-        good = good.contiguous().view(torch.uint8) if good.dtype == torch.bool else (good != 0).to(torch.uint8)
+        good = mask_u8(good)
         kt = c["key_table"]
         with torch.cuda.device(dev):
             check(lib.spacap_caption_select_i32(cap.data_ptr(), nms.data_ptr(), good.data_ptr(), idx.data_ptr(), ids.data_ptr(),
@@ -281,16 +276,9 @@ class CaptionEval:
         """key -> ["sos ... eos"] for every corpus key in corpus order (check_candidates / organize_candidates applied);
         ``idx2word`` maps ``str(id)`` (the reference's vocabulary) or the int id to the word.  One device-to-host copy."""
         if self.cand_tok is None:
-            return {k: ["{} {}".format(_word(idx2word, self.sos), _word(idx2word, self.eos))] for k in self.corpus.keys}
+            return {k: ["{} {}".format(word(idx2word, self.sos), word(idx2word, self.eos))] for k in self.corpus.keys}
         host = torch.cat([self.cand_tok, self.cand_len[:, None]], 1).cpu().numpy()
-        return {k: [" ".join(_word(idx2word, int(t)) for t in host[i, :host[i, LMAX]])] for i, k in enumerate(self.corpus.keys)}
-
-
-def _word(idx2word, i):
-    try:
-        return idx2word[str(i)]
-    except (KeyError, TypeError, IndexError):
-        return idx2word[i]
+        return {k: [" ".join(word(idx2word, int(t)) for t in host[i, :host[i, LMAX]])] for i, k in enumerate(self.corpus.keys)}
 
 
 def corpus_bleu(totals):

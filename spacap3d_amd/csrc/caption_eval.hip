@@ -8,7 +8,8 @@
 //     proposal the stamp base + b*K + k + 1 (base = the proposals of all earlier calls, kept ON THE DEVICE so that a captured
 //     call replays with the right value) and takes the maximum per key row (global integer atomicMax: the result is the same
 //     for every schedule).  Pass two, one wave per proposal, lets only the holder of a row's stamp write the row: sos, the
-//     tokens up to and including the first eos, an eos appended when there was none; one lane per position, plain stores.
+//     tokens up to and including the first eos, an eos appended when there was none (decode_caption of eval_common.hpp, as
+//     predictions.hip writes its captions); one lane per position, plain stores.
 //     The two cells of `counter` hand the base from call to call without a race: pass one reads [0] and writes [1] =
 //     base + B*K, pass two reads [1] and writes [0] = [1].
 //  2. caption_score_kernel (spacap_caption_score_f64), one wave per key row, one lane per token position, no state between
@@ -23,9 +24,11 @@
 // reference's order: bit-equal to Python's.  CIDEr's sums run in wave-reduction order, not the reference's dict order.
 #include <math.h>
 
-#include "common.hpp"
+#include "eval_common.hpp"
 
 namespace {
+
+using namespace spacap::eval;
 
 constexpr int CE_LMAX = 64;                         // tokens per sentence = lanes of a wave = bits of the LCS word
 constexpr double CE_BETA2 = 1.2 * 1.2;              // rouge.py: self.beta ** 2
@@ -72,15 +75,9 @@ __global__ __launch_bounds__(CE_LMAX) void caption_write_kernel(SelectArgs a) {
   if (p == 0 && lane == 0) a.counter[0] = next;                    // (nobody reads [0] in this pass)
   const int row = caption_row(a, p / a.K, p);                      // uniform over the wave
   if (row < 0 || a.stamp[row] != next - (unsigned long long)n + (unsigned long long)p + 1ull) return;
-  const int tok = lane < a.L ? (int)a.tokens[(size_t)p * a.L + lane] : 0;
-  const unsigned long long hit = __ballot(lane < a.L && tok == a.eos);
-  const int first = hit ? __ffsll((long long)hit) - 1 : -1;        // position of the first eos
-  const int body = first >= 0 ? first + 1 : a.L;                   // tokens kept (the eos included)
-  const int len = 1 + body + (first >= 0 ? 0 : 1);                 // <= L + 2 <= 64
-  int32_t *o = a.cand_tok + (size_t)row * CE_LMAX;
-  const int prev = __shfl(tok, lane > 0 ? lane - 1 : 0);           // token lane-1 sits at position lane
-  const int v = lane == 0 ? a.sos : (lane <= body ? prev : a.eos);
-  o[lane] = lane < len ? v : 0;
+  const int tok = lane < a.L ? (int)a.tokens[(size_t)p * a.L + lane] : 0;   // (a token is compared as the int it is stored as)
+  int len;
+  a.cand_tok[(size_t)row * CE_LMAX + lane] = decode_caption(tok, lane, a.L, a.sos, a.eos, len);
   if (lane == 0) a.cand_len[row] = len;
 }
 

@@ -11,7 +11,8 @@
 //     - records of the (scene, class): per-class mode -- every valid box, scored conf[b,k,class]; single-class mode -- the
 //       valid boxes whose sem_cls is the class, scored obj_prob[b,k];
 //     - order: score descending compared as f32, equal scores LOWER proposal index first, NaN behind every number (the
-//       reference's np.argsort(-confidence) is a quicksort: the order of ties is unspecified there), by rank counting;
+//       reference's np.argsort(-confidence) is a quicksort: the order of ties is unspecified there), by rank counting over
+//       one folded u32 key per proposal (rank_key / rank_count of eval_common.hpp, as predictions.hip ranks);
 //     - per record ovmax / jmax over the class's boxes in index order with `iou > ovmax` from -inf (first strict maximum);
 //       the IoU is box3d_iou in f64 in its operation order, IEEE division (a pair without overlap yields its exact +0
 //       without dividing);
@@ -30,9 +31,11 @@
 // bit-equal to numpy's; the area is summed in a fixed order (per thread, then a tree) that is not numpy's pairwise order.
 #include <math.h>
 
-#include "common.hpp"
+#include "eval_common.hpp"
 
 namespace {
+
+using namespace spacap::eval;
 
 constexpr int AP_MAXK = 512;
 constexpr int AP_MAXM = 256;
@@ -43,27 +46,6 @@ constexpr int AP_EXISTS = 0x80;
 constexpr int CURVE_THREADS = 256;
 constexpr int CURVE_ITEMS = 4;
 constexpr int CURVE_TILE = CURVE_THREADS * CURVE_ITEMS;
-
-__device__ __forceinline__ void ap_bounds(const double *__restrict__ c, double lo[3], double hi[3]) {
-#pragma unroll
-  for (int d = 0; d < 3; ++d) lo[d] = hi[d] = c[d];
-#pragma unroll
-  for (int v = 1; v < 8; ++v)
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const double x = c[v * 3 + d];
-      lo[d] = x < lo[d] ? x : lo[d];
-      hi[d] = x > hi[d] ? x : hi[d];
-    }
-}
-
-// does record j come before record k?  (descending score, NaN last, ties: lower proposal index first)
-__device__ __forceinline__ bool ap_ahead(float sj, int j, float sk, int k) {
-  const bool nj = sj != sj, nk = sk != sk;
-  if (nj != nk) return nk;
-  if (!nj && sj != sk) return sj > sk;
-  return j < k;
-}
 
 struct MatchArgs {
   const double *corners;        // [B,K,8,3]
@@ -85,8 +67,7 @@ struct MatchArgs {
 __global__ __launch_bounds__(AP_MAXK) void detection_match_kernel(MatchArgs a) {
   __shared__ double s_gb[6][AP_MAXM];               // bounds of the class's ground-truth boxes, compacted in index order
   __shared__ double s_gvol[AP_MAXM];
-  __shared__ float s_score[AP_MAXK];
-  __shared__ uint8_t s_ex[AP_MAXK];
+  __shared__ __attribute__((aligned(16))) unsigned s_key[AP_MAXK];   // rank_key of every proposal
   __shared__ uint8_t s_gsel[AP_MAXM];
   __shared__ unsigned s_min[AP_MAXT][AP_MAXM];      // per (threshold, box): lowest rank among the records matching it
   const int c = blockIdx.x, b = blockIdx.y, k = threadIdx.x, K = a.K, M = a.M;
@@ -114,9 +95,9 @@ __global__ __launch_bounds__(AP_MAXK) void detection_match_kernel(MatchArgs a) {
       ex = ex && a.sem_cls[p] == (int64_t)c;
       score = a.obj_prob[p];
     }
-    s_score[k] = score;
-    s_ex[k] = ex ? 1 : 0;
   }
+  const unsigned key = rank_key(ex, score);
+  s_key[k] = key;                                   // (threads k >= K: 0, they pad the last group of four)
   __syncthreads();
 
   int G = 0;                                        // ground-truth boxes of the class (uniform over the workgroup)
@@ -125,7 +106,7 @@ __global__ __launch_bounds__(AP_MAXK) void detection_match_kernel(MatchArgs a) {
     for (int m = 0; m < k; ++m) pos += s_gsel[m];
     if (s_gsel[k]) {
       double lo[3], hi[3];
-      ap_bounds(a.gt_corners + ((size_t)b * M + k) * 24, lo, hi);
+      box_bounds(a.gt_corners + ((size_t)b * M + k) * 24, lo, hi);
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
         s_gb[d][pos] = lo[d];
@@ -137,15 +118,8 @@ __global__ __launch_bounds__(AP_MAXK) void detection_match_kernel(MatchArgs a) {
   for (int m = 0; m < M; ++m) G += s_gsel[m];
   for (int i = k; i < AP_MAXT * AP_MAXM; i += AP_MAXK) s_min[i / AP_MAXM][i % AP_MAXM] = 0xFFFFFFFFu;
 
-  // position in the slab: existing records by rank, then the others by proposal index
-  int pos = 0;
-  if (act) {
-    if (ex) {
-      for (int j = 0; j < K; ++j) pos += (s_ex[j] && ap_ahead(s_score[j], j, score, k)) ? 1 : 0;
-    } else {
-      for (int j = 0; j < K; ++j) pos += (s_ex[j] || j < k) ? 1 : 0;
-    }
-  }
+  // position in the slab: existing records by rank, then the others (key 0) by proposal index
+  const int pos = act ? rank_count(s_key, K, key, k) : 0;
   __syncthreads();
 
   // box3d_iou(prediction, ground truth) over the class's boxes: first strict maximum
@@ -153,7 +127,7 @@ __global__ __launch_bounds__(AP_MAXK) void detection_match_kernel(MatchArgs a) {
   int jmax = 0;
   if (ex && G > 0) {
     double lo[3], hi[3];
-    ap_bounds(a.corners + p * 24, lo, hi);
+    box_bounds(a.corners + p * 24, lo, hi);
     const double vol1 = (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
     for (int g = 0; g < G; ++g) {
       double e[3];

@@ -23,9 +23,11 @@
 // few ulp, not bit for bit.
 #include <math.h>
 
-#include "common.hpp"
+#include "eval_common.hpp"
 
 namespace {
+
+using namespace spacap::eval;
 
 constexpr int PIB_THREADS = 256;
 constexpr int PIB_PPT = 4;                          // points per thread
@@ -33,19 +35,6 @@ constexpr int PIB_POINTS = PIB_THREADS * PIB_PPT;   // points per workgroup (one
 constexpr int PP_MAXK = 512;
 constexpr int PP_WORDS = PP_MAXK / 64;
 constexpr int PP_MAXNC = 128;                       // numpy's pairwise-sum block: one block = its 8-accumulator order
-
-__device__ __forceinline__ void box_bounds(const double *__restrict__ c, double lo[3], double hi[3]) {
-#pragma unroll
-  for (int d = 0; d < 3; ++d) lo[d] = hi[d] = c[d];
-#pragma unroll
-  for (int v = 1; v < 8; ++v)
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const double x = c[v * 3 + d];
-      lo[d] = x < lo[d] ? x : lo[d];
-      hi[d] = x > hi[d] ? x : hi[d];
-    }
-}
 
 __global__ __launch_bounds__(PIB_THREADS) void points_in_box_kernel(const float *__restrict__ pc, int N, int C,
                                                                       const double *__restrict__ corners, int K, int nchunk,

@@ -4,23 +4,22 @@
 // (scene, proposal).  No ground truth is involved.
 //
 // dense_caption_select_kernel, one workgroup of 512 threads per scene, one thread per proposal (K <= 512):
-//  1. every thread turns (valid, obj_prob) into ONE sortable u32 in LDS: 0 for a proposal that is not kept, 1 for a kept NaN,
-//     else the f32 bit pattern folded so that unsigned order = numeric order (-0 counts as +0; the smallest such key, that of
-//     -inf, is 0x007FFFFF).  Proposal j is ahead of kept proposal k when key[j] > key[k], or the keys are equal and j < k:
-//     descending score compared as f32, equal scores lower proposal index first, NaN behind every number, and a proposal
-//     that is not kept ahead of nobody -- the order of detection_ap.hip, one LDS array instead of its two.
-//  2. rank counting: a kept thread counts the proposals ahead of it.  All lanes read the same address, so the reads
-//     broadcast; they are 16 bytes wide (four keys per ds_read_b128).  The rank of a kept proposal counts kept proposals
-//     only: the kept rows are dense from 0.  s_src[rank] = proposal.
+//  1. every thread turns (valid, obj_prob) into ONE sortable u32 in LDS (rank_key of eval_common.hpp, the order
+//     detection_ap.hip ranks by too): descending score compared as f32, equal scores lower proposal index first, NaN behind
+//     every number, and a proposal that is not kept ahead of nobody.
+//  2. rank counting (rank_count of eval_common.hpp): a kept thread counts the proposals ahead of it.  The rank of a kept
+//     proposal counts kept proposals only: the kept rows are dense from 0.  s_src[rank] = proposal.
 //  3. outputs by RANK, every element of every array on every call (rows behind the count: index -1, everything else zero):
 //     count / index / score / cls / length one thread per row; the corners as 16-byte chunks (12 per 192-byte box, one per
 //     thread-iteration: a wave stores 1 KiB contiguously); the captions one wave per row and one lane per position, by
-//     decode_caption's rule as caption_eval.hip applies it -- sos, the tokens through the first eos inclusive, an eos appended
-//     when there was none, zero padding (length counts sos and eos).
+//     decode_caption of eval_common.hpp -- sos, the tokens through the first eos inclusive, an eos appended when there was
+//     none, zero padding (length counts sos and eos).
 // No global atomics, no state between calls, no host synchronisation; plain vector loads and stores only.
-#include "common.hpp"
+#include "eval_common.hpp"
 
 namespace {
+
+using namespace spacap::eval;
 
 constexpr int DP_MAXK = 512;
 constexpr int DP_MAXL = 62;                         // L + 2 positions = the lanes of a wave
@@ -42,13 +41,6 @@ struct PredArgs {
   int32_t *length;              // [B,K]
 };
 
-__device__ __forceinline__ unsigned rank_key(bool kept, float s) {
-  if (!kept) return 0u;
-  if (s != s) return 1u;
-  const unsigned u = s == 0.f ? 0u : __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ __launch_bounds__(DP_MAXK) void dense_caption_select_kernel(PredArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned s_key[DP_MAXK];
   __shared__ float s_score[DP_MAXK];
@@ -67,18 +59,8 @@ __global__ __launch_bounds__(DP_MAXK) void dense_caption_select_kernel(PredArgs 
   s_score[k] = score;
   const int count = __syncthreads_count(kept);      // (also the barrier behind the LDS writes)
 
-  if (kept) {
-    int pos = 0;
-    const uint4 *k4 = reinterpret_cast<const uint4 *>(s_key);
-    for (int j = 0; j < K; j += 4) {
-      const uint4 q = k4[j >> 2];
-      pos += (q.x > key || (q.x == key && j < k)) ? 1 : 0;
-      pos += (q.y > key || (q.y == key && j + 1 < k)) ? 1 : 0;
-      pos += (q.z > key || (q.z == key && j + 2 < k)) ? 1 : 0;
-      pos += (q.w > key || (q.w == key && j + 3 < k)) ? 1 : 0;
-    }
-    s_src[pos] = k;                                 // pos < count <= K: ranks of kept proposals are a permutation of 0..count-1
-  }
+  // pos < count <= K: the ranks of the kept proposals are a permutation of 0..count-1
+  if (kept) s_src[rank_count(s_key, K, key, k)] = k;
   __syncthreads();
 
   if (k == 0) a.count[b] = count;
@@ -103,15 +85,8 @@ __global__ __launch_bounds__(DP_MAXK) void dense_caption_select_kernel(PredArgs 
   for (int r = k >> 6; r < K; r += DP_MAXK / 64) {  // (uniform over the wave)
     int v = 0, len = 0;
     if (r < count) {
-      const int64_t t64 = lane < L ? a.tokens[(row0 + s_src[r]) * L + lane] : 0;
-      const int tok = (int)t64;
-      const unsigned long long hit = __ballot(lane < L && t64 == (int64_t)a.eos);
-      const int first = hit ? __ffsll((long long)hit) - 1 : -1;        // position of the first eos
-      const int body = first >= 0 ? first + 1 : L;                     // tokens kept (the eos included)
-      len = 1 + body + (first >= 0 ? 0 : 1);                           // <= L + 2 <= 64
-      const int prev = __shfl(tok, lane > 0 ? lane - 1 : 0);           // token lane-1 sits at position lane
-      v = lane == 0 ? a.sos : (lane <= body ? prev : a.eos);
-      v = lane < len ? v : 0;
+      const int64_t tok = lane < L ? a.tokens[(row0 + s_src[r]) * L + lane] : 0;
+      v = decode_caption(tok, lane, L, a.sos, a.eos, len);
     }
     if (lane < W) a.out_tokens[(row0 + r) * W + lane] = v;
     if (lane == 0) a.length[row0 + r] = len;

@@ -20,16 +20,11 @@ import ctypes
 import numpy as np
 import torch
 
+from ._eval_util import MAX_PROPOSALS, gpu, mask_u8, ptr
 from ._native import check, lib
 
-MAX_PROPOSALS, MAX_GT, MAX_CLASSES, MAX_THRESHOLDS = 512, 256, 128, 4
+MAX_GT, MAX_CLASSES, MAX_THRESHOLDS = 256, 128, 4
 EXISTS = 0x80   # SPACAP_AP_EXISTS of include/spacap_hip.h
-
-
-def _gpu(t, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"detection_ap: {name}: CPU not supported")
-    return t
 
 
 def parse_groundtruths(end_points, config_dict=None):
@@ -81,12 +76,12 @@ class DetectionAP:
         ``obj_prob``); ``end_points``: ``bbox_corner`` (B,K,8,3), ``sem_cls`` (B,K), ``gt_box_corner_label`` (B,M,8,3),
         ``sem_cls_label`` (B,M), ``box_label_mask`` (B,M).  One launch on the current stream, no host synchronisation;
         batches may differ in B.  Returns the batch's slab (score, flags, index)."""
-        corners = _gpu(end_points["bbox_corner"], "bbox_corner")
+        corners = gpu("detection_ap", end_points["bbox_corner"], "bbox_corner")
         dev = corners.device
-        valid = _gpu(post["valid"], "valid")
-        gt = _gpu(end_points["gt_box_corner_label"], "gt_box_corner_label")
-        gt_cls = _gpu(end_points["sem_cls_label"], "sem_cls_label")
-        gt_mask = _gpu(end_points["box_label_mask"], "box_label_mask")
+        valid = gpu("detection_ap", post["valid"], "valid")
+        gt = gpu("detection_ap", end_points["gt_box_corner_label"], "gt_box_corner_label")
+        gt_cls = gpu("detection_ap", end_points["sem_cls_label"], "sem_cls_label")
+        gt_mask = gpu("detection_ap", end_points["box_label_mask"], "box_label_mask")
         if corners.dim() != 4 or tuple(corners.shape[2:]) != (8, 3):
             raise RuntimeError(f"detection_ap: bbox_corner must be (B, K, 8, 3), got {tuple(corners.shape)}")
         B, K = corners.shape[:2]
@@ -99,20 +94,19 @@ class DetectionAP:
             raise RuntimeError(f"detection_ap: valid must be (B, K) = ({B}, {K}), got {tuple(valid.shape)}")
         conf = obj_prob = sem_cls = None
         if self.per_class_proposal:
-            conf = _gpu(post["conf"], "conf").float().contiguous()
+            conf = gpu("detection_ap", post["conf"], "conf").float().contiguous()
             if tuple(conf.shape) != (B, K, NC):
                 raise RuntimeError(f"detection_ap: conf must be (B, K, num_class) = ({B}, {K}, {NC}), got {tuple(conf.shape)}")
         else:
-            obj_prob = _gpu(post["obj_prob"], "obj_prob").float().contiguous()
-            sem_cls = _gpu(end_points["sem_cls"], "sem_cls").long().contiguous()
+            obj_prob = gpu("detection_ap", post["obj_prob"], "obj_prob").float().contiguous()
+            sem_cls = gpu("detection_ap", end_points["sem_cls"], "sem_cls").long().contiguous()
             if tuple(obj_prob.shape) != (B, K) or tuple(sem_cls.shape) != (B, K):
                 raise RuntimeError(f"detection_ap: obj_prob and sem_cls must be (B, K) = ({B}, {K})")
         corners = corners.double().contiguous()
-        valid = valid.contiguous().view(torch.uint8) if valid.dtype == torch.bool else (valid != 0).to(torch.uint8)
+        valid = mask_u8(valid)
         gt = gt.double().contiguous()                 # BBGT.astype(float)
         gt_cls = gt_cls.long().contiguous()
         gt_mask = (gt_mask == 1).to(torch.uint8).contiguous()
-        ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(dev):
             if self.npos is None:
                 self.npos = torch.zeros(NC, dtype=torch.int32, device=dev)
@@ -162,7 +156,6 @@ class DetectionAP:
             if with_curves:
                 rec = torch.zeros(NC, T, L, dtype=torch.float64, device=dev)     # the kernel writes the first count[c] of a row
                 prec = torch.zeros(NC, T, L, dtype=torch.float64, device=dev)
-            ptr = lambda t: None if t is None else t.data_ptr()
             check(lib.spacap_ap_curve_f64(flags.data_ptr(), L, count.data_ptr(), self.npos.data_ptr(), NC, T, ptr(rec),
                                           ptr(prec), ap.data_ptr(), last.data_ptr(),
                                           torch.cuda.current_stream(dev).cuda_stream), "spacap_ap_curve_f64")

@@ -755,13 +755,10 @@ class Evaluator:
     def __init__(self, model, graph=True, postprocess=None, detection_ap=None, caption_eval=None, predictions=None):
         self.model = model
         self.post_kw = None
-        if predictions is not None and postprocess is None:
-            raise ValueError("Evaluator: predictions needs postprocess")
+        for name, given in (("predictions", predictions), ("detection_ap", detection_ap), ("caption_eval", caption_eval)):
+            if given is not None and postprocess is None:
+                raise ValueError(f"Evaluator: {name} needs postprocess")
         self.predictions = None if predictions is None else (int(predictions[0]), int(predictions[1]))
-        if detection_ap is not None and postprocess is None:
-            raise ValueError("Evaluator: detection_ap needs postprocess")
-        if caption_eval is not None and postprocess is None:
-            raise ValueError("Evaluator: caption_eval needs postprocess")
         self.detection_ap = detection_ap
         self.caption_eval = caption_eval
         if postprocess is not None:

@@ -16,17 +16,10 @@ Only ``use_3d_nms=True`` is implemented (the 2D bird's-eye NMS raises ``NotImple
 import numpy as np
 import torch
 
+from ._eval_util import MAX_PROPOSALS, gpu, ptr, to_host
 from ._native import check, lib
 
-MAX_PROPOSALS = 512
-
 REMOVE_EMPTY, CLS_NMS, OLD_TYPE, GT_F32 = 1, 2, 4, 8   # SPACAP_PP_* of include/spacap_hip.h
-
-
-def _gpu(t, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"postprocess: {name}: CPU not supported")
-    return t
 
 
 def post_kwargs(config_dict):
@@ -43,10 +36,10 @@ def post_kwargs(config_dict):
 
 def _run(point_clouds, bbox_corner, objectness_scores, sem_cls, sem_cls_scores, nms_iou, cls_nms, old_type,
          remove_empty_box, min_points, conf_thresh, gt_corners=None, object_assignment=None, min_iou=0.5):
-    pc = _gpu(point_clouds, "point_clouds")
+    pc = gpu("postprocess", point_clouds, "point_clouds")
     dev = pc.device
     for name, t in (("bbox_corner", bbox_corner), ("objectness_scores", objectness_scores), ("sem_cls", sem_cls)):
-        _gpu(t, name)
+        gpu("postprocess", t, name)
         if t.device != dev:
             raise RuntimeError(f"postprocess: {name} must be on {dev}")
     if pc.dim() != 3 or pc.shape[2] < 3:
@@ -61,14 +54,14 @@ def _run(point_clouds, bbox_corner, objectness_scores, sem_cls, sem_cls_scores, 
     corners = bbox_corner.double().contiguous()
     obj = objectness_scores.float().contiguous()
     cls = sem_cls.long().contiguous()
-    scores = None if sem_cls_scores is None else _gpu(sem_cls_scores, "sem_cls_scores").float().contiguous()
+    scores = None if sem_cls_scores is None else gpu("postprocess", sem_cls_scores, "sem_cls_scores").float().contiguous()
     NC = 0 if scores is None else scores.shape[-1]
     flags = (REMOVE_EMPTY if remove_empty_box else 0) | (CLS_NMS if cls_nms else 0) | (OLD_TYPE if old_type else 0)
     gt = oa = None
     M = 0
     if gt_corners is not None:
-        _gpu(gt_corners, "gt_box_corner_label")
-        _gpu(object_assignment, "object_assignment")
+        gpu("postprocess", gt_corners, "gt_box_corner_label")
+        gpu("postprocess", object_assignment, "object_assignment")
         if gt_corners.dtype == torch.float32:
             flags |= GT_F32
         gt = gt_corners.double().contiguous()   # widened once; the f32 volume is restated in the kernel (GT_F32)
@@ -88,7 +81,6 @@ def _run(point_clouds, bbox_corner, objectness_scores, sem_cls, sem_cls_scores, 
         if gt is not None:
             iou = torch.empty(B, K, dtype=torch.float64, device=dev)
             good = torch.empty(B, K, **u8)
-        ptr = lambda t: None if t is None else t.data_ptr()
         check(lib.spacap_points_in_box_f32(pc.data_ptr(), B, N, C, corners.data_ptr(), K, ws.data_ptr(), ws.numel(), stream),
               "spacap_points_in_box_f32")
         check(lib.spacap_detection_nms_f32(obj.data_ptr(), cls.data_ptr(), ptr(scores), NC, corners.data_ptr(), ws.data_ptr(),
@@ -141,18 +133,9 @@ def parse_predictions(end_points, config_dict):
     r = detection_postprocess(end_points["point_clouds"], end_points["bbox_corner"], end_points["objectness_scores"],
                               end_points["sem_cls"], end_points["sem_cls_scores"] if per_class else None, **kw)
     B, K = r["pred_mask"].shape
-    parts = [r["pred_mask"].to(torch.uint8), r["valid"].to(torch.uint8), r["obj_prob"],
-             end_points["sem_cls"].long(), end_points["bbox_corner"].double()]
-    if per_class:
-        parts.append(r["conf"])
     # one device-to-host copy of everything the lists are built from
-    flat = torch.cat([p.contiguous().reshape(-1).view(torch.uint8) for p in parts]).cpu().numpy()
-    host, off = [], 0
-    for p in parts:
-        nb = p.numel() * p.element_size()
-        host.append(flat[off:off + nb].view({torch.uint8: np.uint8, torch.float32: np.float32, torch.int64: np.int64,
-                                             torch.float64: np.float64}[p.dtype]).reshape(tuple(p.shape)))
-        off += nb
+    host = to_host([r["pred_mask"].to(torch.uint8), r["valid"].to(torch.uint8), r["obj_prob"],
+                    end_points["sem_cls"].long(), end_points["bbox_corner"].double()] + ([r["conf"]] if per_class else []))
     pred, valid, obj_prob, sem_cls, corners = host[:5]
     pred_mask = pred.astype(np.float64)
     end_points["pred_mask"] = pred_mask

@@ -14,20 +14,13 @@ instead of in proposal order -- ``proposal`` names the original index; words are
 
 CPU tensors raise ``RuntimeError("... CPU not supported")``: there is no host fallback.
 """
-import numpy as np
 import torch
 
+from ._eval_util import MAX_PROPOSALS, gpu, mask_u8, to_host, word
 from ._native import check, lib
-from .postprocess import MAX_PROPOSALS
 
 MAX_TOKENS = 62      # L + 2 positions = one wave (csrc/predictions.hip)
 KEYS = ("count", "index", "score", "cls", "corners", "tokens", "length")
-
-
-def _gpu(t, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"predictions: {name}: CPU not supported")
-    return t
 
 
 def _aligned(t):
@@ -45,12 +38,12 @@ def dense_caption_predictions(post, out, sos, eos, into=None):
     f32 (B,K), ``cls`` i32 (B,K), ``corners`` f64 (B,K,8,3), ``tokens`` i32 (B,K,L+2) = sos, the words through the first eos,
     an eos appended when there was none, zeros, and ``length`` i32 (B,K) (sos and eos included); rows behind ``count`` are
     zero."""
-    valid = _gpu(post["valid"], "valid")
+    valid = gpu("predictions", post["valid"], "valid")
     dev = valid.device
-    prob = _gpu(post["obj_prob"], "obj_prob")
-    corners = _gpu(out["bbox_corner"], "bbox_corner")
-    cls = _gpu(out["sem_cls"], "sem_cls")
-    cap = _gpu(out["lang_cap"], "lang_cap")
+    prob = gpu("predictions", post["obj_prob"], "obj_prob")
+    corners = gpu("predictions", out["bbox_corner"], "bbox_corner")
+    cls = gpu("predictions", out["sem_cls"], "sem_cls")
+    cap = gpu("predictions", out["lang_cap"], "lang_cap")
     for name, t in (("obj_prob", prob), ("bbox_corner", corners), ("sem_cls", cls), ("lang_cap", cap)):
         if t.device != dev:
             raise RuntimeError(f"predictions: {name} must be on {dev}")
@@ -75,7 +68,7 @@ def dense_caption_predictions(post, out, sos, eos, into=None):
     sos, eos = int(sos), int(eos)
     if not (0 <= sos < 2 ** 31 and 0 <= eos < 2 ** 31):
         raise RuntimeError(f"predictions: sos={sos} / eos={eos} must be word ids (0 <= id < 2^31)")
-    valid = valid.contiguous().view(torch.uint8) if valid.dtype == torch.bool else (valid != 0).to(torch.uint8)
+    valid = mask_u8(valid)
     prob = prob.float().contiguous()
     cls = cls.long().contiguous()
     cap = cap.long().contiguous()
@@ -87,7 +80,7 @@ def dense_caption_predictions(post, out, sos, eos, into=None):
         if into is None:
             r = {k: torch.empty(s, dtype=dt, device=dev) for k, (s, dt) in shapes.items()}
         else:
-            r = {k: _gpu(into[k], k) for k in KEYS}
+            r = {k: gpu("predictions", into[k], k) for k in KEYS}
             for k, (s, dt) in shapes.items():
                 if tuple(r[k].shape) != s or r[k].dtype != dt or r[k].device != dev or not r[k].is_contiguous() \
                         or (k == "corners" and r[k].data_ptr() % 16):
@@ -98,27 +91,13 @@ def dense_caption_predictions(post, out, sos, eos, into=None):
     return r
 
 
-def _word(idx2word, i):
-    try:
-        return idx2word[str(i)]
-    except (KeyError, TypeError, IndexError):
-        return idx2word[i]
-
-
 def to_records(pred, idx2word=None, class2type=None):
     """The dict of ``dense_caption_predictions`` as one list of dicts per scene, best box first: ``proposal`` (its index among
     the K proposals), ``score`` (float), ``sem_cls`` (int; ``class_name`` = ``class2type[sem_cls]`` when the map is given),
     ``corners`` ((8,3) f64 array), ``tokens`` (list of ints, sos .. eos) and, when ``idx2word`` is given (``str(id)`` or the
     int id -> word), ``caption`` = the string ``"sos ... eos"``.  A scene with nothing kept gives an empty list.  One
     device-to-host copy."""
-    parts = [_gpu(pred[k], k).contiguous() for k in KEYS]
-    flat = torch.cat([p.reshape(-1).view(torch.uint8) for p in parts]).cpu().numpy()
-    host, off = {}, 0
-    for k, p in zip(KEYS, parts):
-        nb = p.numel() * p.element_size()
-        host[k] = flat[off:off + nb].view({torch.int32: np.int32, torch.float32: np.float32,
-                                           torch.float64: np.float64}[p.dtype]).reshape(tuple(p.shape))
-        off += nb
+    host = to_host({k: gpu("predictions", pred[k], k) for k in KEYS})
     scenes = []
     for b in range(host["count"].shape[0]):
         cur = []
@@ -130,7 +109,7 @@ def to_records(pred, idx2word=None, class2type=None):
             if class2type is not None:
                 rec["class_name"] = class2type[c]
             if idx2word is not None:
-                rec["caption"] = " ".join(_word(idx2word, t) for t in toks)
+                rec["caption"] = " ".join(word(idx2word, t) for t in toks)
             cur.append(rec)
         scenes.append(cur)
     return scenes

@@ -136,6 +136,33 @@ def test_matches_restatement(name):
     _check(ap, slabs, npos, nc, len(thr))
 
 
+@pytest.mark.parametrize("per_class", [True, False])
+def test_rank_order_with_special_scores_and_k_not_a_multiple_of_four(per_class):
+    """The order inside a (scene, class) for scores that only the comparison rules tell apart -- NaN, both infinities, both
+    zeros, a denormal, repeated values -- among valid and not-valid proposals alike, at a K whose last group of four
+    proposals is incomplete.  Slabs and npos equal the restatement exactly."""
+    B, K, M, nc, thr = 2, 37, 5, 3, (0.25, 0.5)
+    pool = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 1e-40, 0.5, 0.5, 0.25, 0.25, 0.75], np.float32)
+    assert pool[5] != 0 and np.abs(pool[5]) < np.finfo(np.float32).tiny
+    d = synthetic(B, K, M, nc, seed=7, live=1.1)
+    b, k, c = np.arange(B)[:, None, None], np.arange(K)[None, :, None], np.arange(nc)[None, None, :]
+    d["conf"] = pool[(k + 2 * c + b) % len(pool)]
+    d["obj_prob"] = pool[(k + b)[:, :, 0] % len(pool)]
+    d["valid"] = ((k // len(pool) + b) % 2 == 0)[:, :, 0]            # every pool value sits in valid and not-valid proposals
+    d["sem_cls"] = d["sem_cls"] % 2                                  # single-class mode: long lists, and a class without records
+    for s in (d["obj_prob"], d["conf"][:, :, 0]):
+        for v in pool.view(np.uint32):
+            hit = s.view(np.uint32) == v
+            assert (hit & d["valid"]).any() and (hit & ~d["valid"]).any()
+    ap = _run(d, [B], per_class, nc, thr)
+    slabs, npos = _restated(d, [B], per_class, nc, thr)
+    assert (slabs[0][1] & 3).any() and (slabs[0][1] == R.EXISTS).any() and (slabs[0][1] == 0).any()
+    for g, w, what in zip(ap.slabs[0], slabs[0], ("score", "flags", "index")):
+        np.testing.assert_array_equal(g.cpu().numpy(), w, err_msg=what)                 # (NaN equals NaN)
+    np.testing.assert_array_equal(np.signbit(ap.slabs[0][0].cpu().numpy()), np.signbit(slabs[0][0]), err_msg="sign of zero")
+    np.testing.assert_array_equal(ap.npos.cpu().numpy(), npos)
+
+
 def test_one_batch_equals_split_steps_and_reset_starts_over():
     d = synthetic(5, 128, 32, 18, seed=3, quant=64)
     whole = _run(d, [5], True)

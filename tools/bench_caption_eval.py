@@ -18,7 +18,8 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _eval_bench import ROOT, enter_reference, replay_us
+
 sys.path.insert(0, ROOT)
 SOS, EOS, V, B, K, L = 2, 3, 3000, 8, 256, 31
 
@@ -53,7 +54,7 @@ def strings(refs, cands):
 
 
 def reference_baseline(ref_dir, nk):
-    sys.path.insert(0, ref_dir)
+    enter_reference(ref_dir)
     import lib.capeval.bleu.bleu as capbleu
     import lib.capeval.cider.cider as capcider
     import lib.capeval.rouge.rouge as caprouge
@@ -88,41 +89,16 @@ def device_times(iters, nk):
     d = {"lang_cap": up(tokens), "dataset_idx": up(rng.integers(0, n_items, B)), "scene_object_ids": up(rng.integers(0, n_obj, (B, 128))),
          "object_assignment": up(rng.integers(0, 128, (B, K))), "nms_masks": up((rng.random((B, K)) < 0.3).astype(np.int64)),
          "good_bbox_masks": up(rng.random((B, K)) < 0.5)}
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-    def replay_us(fn):
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(3):
-                fn()
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            keep = fn()
-        for _ in range(20):
-            g.replay()
-        us = []
-        for _ in range(5):
-            t0.record()
-            for _ in range(iters):
-                g.replay()
-            t1.record()
-            t1.synchronize()
-            us.append(t0.elapsed_time(t1) * 1e3 / iters)
-        del keep
-        return round(float(np.median(us)), 2)
-
-    step_us = replay_us(lambda: ce.step(d, masks=d))
-    print(json.dumps({"what": "CaptionEval.step", "B": B, "K": K, "L": L, "keys": nk, "device_us_per_batch": step_us,
+    step_us, _ = replay_us(lambda: ce.step(d, masks=d), iters, settle=20)
+    print(json.dumps({"what": "CaptionEval.step", "B": B, "K": K, "L": L, "keys": nk, "device_us_per_batch": round(step_us, 2),
                       "iters": iters}), flush=True)
     tok = np.zeros((nk, LMAX), np.int32)
     for i, c in enumerate(cands):
         tok[i, :len(c)] = c
     ce.set_candidates(up(tok), up(np.array([len(c) for c in cands], np.int32)))
-    score_us = replay_us(ce.scores)
+    score_us, _ = replay_us(ce.scores, iters, settle=20)
     print(json.dumps({"what": "scoring launch (spacap_caption_score_f64)", "keys": nk, "references": int(co.ref_len.size),
-                      "device_us": score_us, "iters": iters}), flush=True)
+                      "device_us": round(score_us, 2), "iters": iters}), flush=True)
     ms = []
     for _ in range(7):
         torch.cuda.synchronize()

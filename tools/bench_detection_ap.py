@@ -18,7 +18,8 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _eval_bench import ROOT, eager_us, enter_reference, replay_us
+
 sys.path.insert(0, ROOT)
 NC, M, THRESHOLDS = 18, 128, (0.25, 0.5)
 
@@ -45,11 +46,7 @@ def scenes(B, K, seed):
 
 
 def reference_baseline(ref_dir, n_scenes, K):
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    from make_fixtures_postprocess import install_stubs   # stand-ins for modules the reference imports and does not use here
-    install_stubs()
-    os.chdir(ref_dir)
-    sys.path.insert(0, ref_dir)
+    enter_reference(ref_dir)
     import torch
     from lib.ap_helper import APCalculator, parse_groundtruths
     calcs = [APCalculator(t, None) for t in THRESHOLDS]
@@ -86,44 +83,15 @@ def device_times(iters, n_scenes):
     from spacap3d_amd.detection_ap import DetectionAP
     dev = "cuda:0"
     to = lambda d: {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in d.items()}
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for name, K in (("cfg2", 256), ("cfg5", 512)):
         d = to(scenes(8, K, seed=0))
         ap = DetectionAP(NC, THRESHOLDS)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(3):
-                ap.step(d, d)
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            ap.step(d, d)
-        dev_us = []
-        for _ in range(5):
-            t0.record()
-            for _ in range(iters):
-                g.replay()
-            t1.record()
-            t1.synchronize()
-            dev_us.append(t0.elapsed_time(t1) * 1e3 / iters)
-        # the launch alone: inputs already in the kernel's dtypes, so the graph holds nothing but the match kernel
-        dk = dict(d, bbox_corner=d["bbox_corner"].double(), gt_box_corner_label=d["gt_box_corner_label"].double())
-        g2 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g2):
-            ap.step(dk, dk)
-        call_us = []
-        for _ in range(iters):
-            ap.reset()
-            torch.cuda.synchronize()
-            t0.record()
-            ap.step(d, d)
-            t1.record()
-            t1.synchronize()
-            call_us.append(t0.elapsed_time(t1) * 1e3)
+        step = lambda: ap.step(d, d)
+        dev_us, _ = replay_us(step, iters)
+        call_us = eager_us(step, iters, before=ap.reset)
         print(json.dumps({"shape": name, "B": 8, "K": K, "M": M, "NC": NC, "thresholds": len(THRESHOLDS),
-                          "device_us_per_batch": round(float(np.median(dev_us)), 1),
-                          "eager_call_us": round(float(np.median(call_us)), 1), "iters": iters}), flush=True)
+                          "device_us_per_batch": round(dev_us, 1), "eager_call_us": round(call_us, 1), "iters": iters}),
+              flush=True)
     ap = DetectionAP(NC, THRESHOLDS)
     records = 0
     for i in range(n_scenes // 8):

@@ -6,13 +6,13 @@ Prints one JSON line per shape.
 Run:  timeout -k 10 300 python tools/bench_postprocess.py [--iters 200]"""
 import argparse
 import json
-import os
 import sys
 
-import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _eval_bench import ROOT, eager_us, replay_us
+
+sys.path.insert(0, ROOT)
 from spacap3d_amd.postprocess import detection_postprocess  # noqa: E402
 
 
@@ -35,34 +35,11 @@ def main():
     args = ap.parse_args()
     for name, (B, N, K) in (("cfg2", (8, 40000, 256)), ("cfg5", (8, 80000, 512))):
         inp = scenes(B, N, K)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(3):
-                detection_postprocess(*inp)
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()   # device time: the two launches replayed back to back, no host work in between
-        with torch.cuda.graph(g):
-            detection_postprocess(*inp)
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        dev_us = []
-        for _ in range(5):
-            t0.record()
-            for _ in range(args.iters):
-                g.replay()
-            t1.record()
-            t1.synchronize()
-            dev_us.append(t0.elapsed_time(t1) * 1e3 / args.iters)
-        call_us = []                 # one eager call: the Python wrapper's host work included
-        for _ in range(args.iters):
-            torch.cuda.synchronize()
-            t0.record()
-            detection_postprocess(*inp)
-            t1.record()
-            t1.synchronize()
-            call_us.append(t0.elapsed_time(t1) * 1e3)
-        print(json.dumps({"shape": name, "B": B, "N": N, "K": K, "device_us_per_batch": round(float(np.median(dev_us)), 1),
-                          "eager_call_us": round(float(np.median(call_us)), 1), "iters": args.iters}), flush=True)
+        fn = lambda: detection_postprocess(*inp)
+        dev_us, _ = replay_us(fn, args.iters)   # the two launches replayed back to back
+        call_us = eager_us(fn, args.iters)
+        print(json.dumps({"shape": name, "B": B, "N": N, "K": K, "device_us_per_batch": round(dev_us, 1),
+                          "eager_call_us": round(call_us, 1), "iters": args.iters}), flush=True)
 
 
 if __name__ == "__main__":

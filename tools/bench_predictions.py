@@ -19,7 +19,8 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _eval_bench import ROOT, enter_reference, replay_us
+
 sys.path.insert(0, ROOT)
 SOS, EOS, V, NC, L = 2, 3, 3000, 18, 31
 CONFIGS = {"cfg2": (8, 256, 40000), "cfg5": (8, 512, 80000)}
@@ -39,11 +40,7 @@ def batch(B, K, seed=0):
 
 
 def reference_baseline(ref_dir):
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    from make_fixtures_postprocess import corners_of, install_stubs   # stand-ins for modules the reference imports, unused here
-    install_stubs()
-    os.chdir(ref_dir)
-    sys.path.insert(0, ref_dir)
+    corners_of = enter_reference(ref_dir).corners_of
     import types
     import torch
     import data.scannet.model_util_scannet as mus
@@ -84,33 +81,13 @@ def device_times(iters):
     import torch
     from spacap3d_amd.predictions import dense_caption_predictions, to_records
     dev = "cuda:0"
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     idx2word = {str(i): word(i) for i in range(V)}
     for name, (B, K, _) in CONFIGS.items():
         d = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in batch(B, K).items()}
-        fn = lambda: dense_caption_predictions(d, d, SOS, EOS)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(3):
-                fn()
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            pred = fn()
-        for _ in range(20):
-            g.replay()
-        us = []
-        for _ in range(5):
-            t0.record()
-            for _ in range(iters):
-                g.replay()
-            t1.record()
-            t1.synchronize()
-            us.append(t0.elapsed_time(t1) * 1e3 / iters)
+        us, pred = replay_us(lambda: dense_caption_predictions(d, d, SOS, EOS), iters, settle=20)
         kept = int(pred["count"].sum())
         print(json.dumps({"what": "dense_caption_predictions", "config": name, "B": B, "K": K, "L": L, "kept": kept,
-                          "device_us_per_batch": round(float(np.median(us)), 2), "iters": iters}), flush=True)
+                          "device_us_per_batch": round(us, 2), "iters": iters}), flush=True)
         ms = []
         for _ in range(7):
             torch.cuda.synchronize()
