@@ -41,8 +41,7 @@ using spacap::mfma::f32x4;
 constexpr int STAT_THREADS = 256;
 
 __device__ __forceinline__ double block_sum_f64(double v, double *s_buf) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  v = spacap::wave_sum(v);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   __syncthreads();
   if (lane == 0) s_buf[wid] = v;
@@ -93,16 +92,10 @@ __global__ void bn_stats_final_kernel(const double *__restrict__ part, int C, in
     s += part[((size_t)c * nsplit + p) * 2 + 0];
     q += part[((size_t)c * nsplit + p) * 2 + 1];
   }
-  const double mean = s / M;
-  double var = q / M - mean * mean;
-  if (var < 0.0) var = 0.0;
-  stats[c * 2 + 0] = (float)mean;
-  stats[c * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-  if (running_mean) {
-    const double unbiased = M > 1.0 ? var * M / (M - 1.0) : var;
-    running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
-    running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unbiased);
-  }
+  const spacap::BnChannel bn = spacap::bn_channel(s, q, M, eps);
+  stats[c * 2 + 0] = (float)bn.mean;
+  stats[c * 2 + 1] = bn.istd;
+  if (running_mean) spacap::bn_update_running(bn, M, momentum, running_mean, running_var, c);
 }
 
 // ---- forward apply: out = relu((z - mean) * (invstd * gamma) + beta), rows = (b, c)
@@ -317,18 +310,12 @@ __global__ __launch_bounds__(STAT_THREADS) void bn_relu_train_small_kernel(
   }
   s = block_sum_f64(s, s_buf);
   q = block_sum_f64(q, s_buf);
-  const double mean_d = s / M;
-  double var = q / M - mean_d * mean_d;
-  if (var < 0.0) var = 0.0;
-  const float mean = (float)mean_d, istd = (float)(1.0 / sqrt(var + (double)eps));
+  const spacap::BnChannel bn = spacap::bn_channel(s, q, M, eps);
+  const float mean = (float)bn.mean, istd = bn.istd;
   if (threadIdx.x == 0) {
     stats[c * 2 + 0] = mean;
     stats[c * 2 + 1] = istd;
-    if (running_mean) {
-      const double unbiased = M > 1.0 ? var * M / (M - 1.0) : var;
-      running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean_d);
-      running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unbiased);
-    }
+    if (running_mean) spacap::bn_update_running(bn, M, momentum, running_mean, running_var, c);
   }
   const float sc = istd * gamma[c], sh = beta[c];
   for (long i = threadIdx.x; i < total; i += STAT_THREADS) {

@@ -83,17 +83,6 @@ __global__ __launch_bounds__(CE_LMAX) void caption_write_kernel(SelectArgs a) {
 
 // ---- scoring ---------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 struct ScoreArgs {
   const int32_t *cand_tok;      // [NKEYS, 64]
   const int32_t *cand_len;      // [NKEYS]
@@ -167,7 +156,7 @@ __global__ __launch_bounds__(CE_LMAX) void caption_score_kernel(ScoreArgs a) {
     maxref[n] = 0;
     cidf[n] = in ? idf_lookup(a, n, cc[n]) : 0.0;
     cvec[n] = (double)cnt * cidf[n];
-    cnorm[n] = sqrt(wave_sum_f64(cfirst[n] ? cvec[n] * cvec[n] : 0.0));
+    cnorm[n] = sqrt(spacap::wave_sum(cfirst[n] ? cvec[n] * cvec[n] : 0.0));
     score[n] = 0.0;
   }
   const int len_h = lc > 1 ? lc - 1 : 0;             // the reference's `length`: the number of BIGRAMS
@@ -230,14 +219,14 @@ __global__ __launch_bounds__(CE_LMAX) void caption_score_kernel(ScoreArgs a) {
       const bool rfirst = lane < rvalid && rbefore == 0;
       double rv = 0.0;
       if (rfirst) rv = (double)rcnt * idf_lookup(a, n, rc[n]);
-      const double rnorm = sqrt(wave_sum_f64(rfirst ? rv * rv : 0.0));
+      const double rnorm = sqrt(spacap::wave_sum(rfirst ? rv * rv : 0.0));
       if (cfirst[n]) maxref[n] = cr > maxref[n] ? cr : maxref[n];
       double term = 0.0;
       if (cfirst[n]) {
         const double vr = (double)cr * cidf[n];
         term = (cvec[n] < vr ? cvec[n] : vr) * vr;
       }
-      double val = wave_sum_f64(term);
+      double val = spacap::wave_sum(term);
       if (cnorm[n] != 0.0 && rnorm != 0.0) val /= cnorm[n] * rnorm;
       val *= penalty;
       score[n] += val;
@@ -247,7 +236,7 @@ __global__ __launch_bounds__(CE_LMAX) void caption_score_kernel(ScoreArgs a) {
   int correct[4];
 #pragma unroll
   for (int n = 0; n < 4; ++n)
-    correct[n] = wave_sum_int(cfirst[n] ? (ccount[n] < maxref[n] ? ccount[n] : maxref[n]) : 0);
+    correct[n] = spacap::wave_sum(cfirst[n] ? (ccount[n] < maxref[n] ? ccount[n] : maxref[n]) : 0);
   if (lane == 0) {
     int32_t *o = a.bleu + (size_t)key * 10;
     o[0] = lc;

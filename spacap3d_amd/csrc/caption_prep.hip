@@ -12,34 +12,13 @@
 //   the last workgroup to finish adds up pred = sum_b dist[b] good[b] / max(1, sum_b good[b]) in scene order.
 // Backward: d src = d memory = the indicator row's gradient at (b, idx[b]), zero elsewhere; d E[v] = sum over the positions
 // holding token v, in (scene, position) order, of dropout'(g) * sqrt(D): one workgroup per vocabulary row, no atomics.
-// Dropout is the library's counter hash (elementwise.hip), regenerated in the backward.
+// Dropout is the library's counter hash (dropout.hpp), regenerated in the backward.
 #include "common.hpp"
+#include "dropout.hpp"
 
 namespace {
 
-struct DropSeed {
-  unsigned lo, hi;
-};
-__device__ __forceinline__ DropSeed make_seed(unsigned long long seed, const unsigned long long *seed_dev) {
-  const unsigned long long s = seed + (seed_dev ? *seed_dev * 0x9E3779B97F4A7C15ull : 0ull);
-  return DropSeed{(unsigned)s, (unsigned)(s >> 32)};
-}
-__device__ __forceinline__ unsigned hash32(unsigned long long idx, DropSeed s) {   // murmur3 fmix32, as elementwise.hip
-  unsigned h = (unsigned)idx ^ s.lo;
-  h += ((unsigned)(idx >> 32) ^ s.hi) * 0x9E3779B1u;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
-inline bool drop_params(float p, unsigned &thresh, float &scale) {
-  if (!(p >= 0.f && p < 1.f)) return false;
-  thresh = p > 0.f ? (unsigned)((double)p * 4294967296.0) : 0u;
-  scale = 1.0f / (1.0f - p);
-  return true;
-}
+using namespace spacap;
 
 struct PrepArgs {
   const float *xyz, *ref, *src, *memory, *emb, *pe;

@@ -33,6 +33,12 @@ inline hipError_t allow_dynamic_lds(const void *fn, int bytes, unsigned long lon
   return e;
 }
 
+// true when every pointer is 16-byte aligned (a null pointer counts as aligned: callers test for null themselves)
+template <typename... P>
+inline bool aligned16(const P *...p) {
+  return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
+}
+
 #define SPACAP_REQUIRE(cond, ...)          \
   do {                                     \
     if (!(cond)) {                         \
@@ -117,15 +123,68 @@ __device__ __forceinline__ unsigned wave_min_u32_fast(unsigned v) {
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-__device__ __forceinline__ float wave_max_f32(float v) {
+// Reductions over W adjacent lanes (W = 64: the whole wave) by the xor-shuffle ladder, offsets W/2 .. 1 in that order;
+// every lane ends up with the result.  float / double / int.
+template <int W = 64, typename T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  for (int o = W / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
-__device__ __forceinline__ float wave_sum_f32(float v) {
+template <int W = 64, typename T>
+__device__ __forceinline__ T wave_min(T v) {
 #pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  for (int o = W / 2; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
   return v;
+}
+template <int W = 64, typename T>
+__device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+  for (int o = W / 2; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
+  return v;
+}
+
+// ---- furthest point sampling: the reference's tie-break and its fminf (fps.hip, fps_bucket.inc, tools/lab) ----------------
+// v_min_f32 without the canonicalising v_max hipcc emits in front of fminf (operands are never sNaN there); in IEEE mode
+// it returns the non-NaN operand, i.e. the reference's fminf (sampling_gpu.cu:106).
+__device__ __forceinline__ float vmin_f32(float a, float b) {
+  float r;
+  asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// key(k) orders candidates the way the reference's shared-memory tree does (the lower slot wins at every level): among
+// equal maxima the winner minimises (bitreverse_lg(k mod 2^lg), k div 2^lg); smaller key wins.
+__device__ __forceinline__ unsigned fps_key(int k, int lg) {
+  const unsigned low = (unsigned)k & ((1u << lg) - 1u);
+  const unsigned rev = lg ? (__brev(low) >> (32 - lg)) : 0u;
+  return (rev << 20) | ((unsigned)k >> lg);
+}
+__device__ __forceinline__ int fps_unkey(unsigned key, int lg) {
+  const unsigned rev = key >> 20;
+  const unsigned low = lg ? (__brev(rev) >> (32 - lg)) : 0u;
+  return (int)(((key & 0xFFFFFu) << lg) | low);
+}
+
+// ---- training-mode BatchNorm of one channel from its fp64 (sum, sum of squares) over M elements, torch semantics ----------
+// Two steps, because every caller stores its own statistics record between them: the biased variance, clamped at 0,
+// normalises; the UNBIASED one goes into running_var.  The running statistics are optional in every entry point: callers
+// skip bn_update_running when running_mean is null.  Inline on purpose: both compile under the including file's
+// -ffp-contract flag, as the code they replaced did.
+struct BnChannel {
+  double mean, var;
+  float istd;
+};
+__device__ __forceinline__ BnChannel bn_channel(double sum, double sumsq, double M, float eps) {
+  const double mean = sum / M;
+  double var = sumsq / M - mean * mean;
+  if (var < 0.0) var = 0.0;
+  return BnChannel{mean, var, (float)(1.0 / sqrt(var + (double)eps))};
+}
+__device__ __forceinline__ void bn_update_running(BnChannel bn, double M, float momentum, float *running_mean,
+                                                  float *running_var, int c) {
+  const double unbiased = M > 1.0 ? bn.var * M / (M - 1.0) : bn.var;
+  running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * bn.mean);
+  running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unbiased);
 }
 
 }  // namespace spacap

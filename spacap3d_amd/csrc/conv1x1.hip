@@ -254,7 +254,7 @@ extern "C" int spacap_conv1x1_cm_f32(int mode, const float *W, const float *in, 
   SPACAP_REQUIRE((mode == 0 || mode == 1 || mode == 2) && B >= 0 && spacap_conv1x1_cm_supported(CI, CO, N) && N <= 2147483647L && B <= 65535,
                  "%s: (mode=%d, B=%d, CI=%d, CO=%d, N=%ld) unsupported", what, mode, B, CI, CO, N);
   if (B == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(W && in && out && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+  SPACAP_REQUIRE(W && in && out && spacap::aligned16(in, out),
                  "%s: null or unaligned pointer", what);
   const bool f32fwd = mode == 2;   // mode 2: the forward of mode 0 on the fp32-MFMA kernel whatever the environment says
   if (f32fwd) mode = 0;

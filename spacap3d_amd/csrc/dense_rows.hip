@@ -187,7 +187,6 @@ __global__ __launch_bounds__(256) void dense_sum_slices_kernel(const float *__re
   }
 }
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -229,9 +228,9 @@ extern "C" int spacap_dense_rows_f32(const float *a, long lda, long a_grp, long 
   g.slice_stride = slice_stride;
   g.split_k = batch ? 0 : 1;
   g.a_zstride = batch ? a_zstride : 0, g.w_zstride = batch ? w_zstride : 0;
-  g.vec_a = aligned16(a) && lda % 4 == 0 && (a_grp == 0 || a_gstride % 4 == 0) && g.a_zstride % 4 == 0;
-  g.vec_w = aligned16(W) && ldw % 4 == 0 && g.w_zstride % 4 == 0;
-  g.vec_o = aligned16(out) && ldo % 4 == 0 && (o_grp == 0 || o_gstride % 4 == 0) && (slices == 1 || slice_stride % 4 == 0);
+  g.vec_a = spacap::aligned16(a) && lda % 4 == 0 && (a_grp == 0 || a_gstride % 4 == 0) && g.a_zstride % 4 == 0;
+  g.vec_w = spacap::aligned16(W) && ldw % 4 == 0 && g.w_zstride % 4 == 0;
+  g.vec_o = spacap::aligned16(out) && ldo % 4 == 0 && (o_grp == 0 || o_gstride % 4 == 0) && (slices == 1 || slice_stride % 4 == 0);
   hipStream_t s = spacap::as_stream(stream);
   const bool small = R <= 1024;
   const long tiles = small ? (R + 31) / 32 : (R + 63) / 64;
@@ -252,7 +251,7 @@ extern "C" int spacap_dense_rows_f32(const float *a, long lda, long a_grp, long 
 extern "C" int spacap_dense_sum_slices_f32(const float *parts, int S, long n, long stride, float *out, spacap_stream_t stream) {
   const char *what = "spacap_dense_sum_slices_f32";
   SPACAP_REQUIRE(parts && out && S >= 1 && n >= 0 && stride >= n && stride % 4 == 0 &&
-                     ((reinterpret_cast<uintptr_t>(parts) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+                     spacap::aligned16(parts, out),
                  "%s: bad arguments", what);
   if (n == 0) return SPACAP_OK;
   hipLaunchKernelGGL(dense_sum_slices_kernel, dim3((unsigned)((n / 4 + 256) / 256)), dim3(256), 0, spacap::as_stream(stream), parts, S, n,

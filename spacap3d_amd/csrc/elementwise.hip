@@ -4,37 +4,15 @@
 //   dropout_add  :  out = res + dropout(y)          models/transformer_captioner.py:115-123 (SublayerConnection)
 //
 // PyTorch runs each as two launches forward (and keeps a byte mask for backward); here one launch each way.  The
-// keep mask is a counter hash of (seed, element index) -- regenerated in the backward instead of stored -- with the
-// same two-part seed as the attention dropout (host word per call + device-resident step counter, so a replayed
-// hipGraph draws new masks every step).  Dropout semantics as torch.nn.Dropout: keep with probability 1 - p,
-// scale kept values by 1 / (1 - p).
+// keep mask is the counter hash of dropout.hpp over the flat element index, regenerated in the backward instead of stored.
 #include "common.hpp"
+#include "dropout.hpp"
 #include "mfma.hpp"
 
 namespace {
 
+using namespace spacap;
 using spacap::mfma::f32x4;
-
-struct DropSeed {
-  unsigned lo, hi;
-};
-
-__device__ __forceinline__ DropSeed make_seed(unsigned long long seed, const unsigned long long *seed_dev) {
-  const unsigned long long s = seed + (seed_dev ? *seed_dev * 0x9E3779B97F4A7C15ull : 0ull);
-  return DropSeed{(unsigned)s, (unsigned)(s >> 32)};
-}
-
-// 32-bit finaliser (murmur3 fmix32) over the element index mixed with both seed words
-__device__ __forceinline__ unsigned hash32(unsigned long long idx, DropSeed s) {
-  unsigned h = (unsigned)idx ^ s.lo;
-  h += ((unsigned)(idx >> 32) ^ s.hi) * 0x9E3779B1u;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
 
 template <int MODE>  // 0: y = drop(relu(x)); 1: out = res + drop(x); 2: dx = keep ? g * scale : 0
 __global__ __launch_bounds__(256) void drop_kernel(const float *__restrict__ x, const float *__restrict__ res, long n,
@@ -88,13 +66,6 @@ inline unsigned grid_for(long n) {
   return (unsigned)g;
 }
 
-inline bool drop_params(float p, unsigned &thresh, float &scale) {
-  if (!(p >= 0.f && p < 1.f)) return false;
-  thresh = p > 0.f ? (unsigned)((double)p * 4294967296.0) : 0u;
-  scale = 1.0f / (1.0f - p);
-  return true;
-}
-
 }  // namespace
 
 #define DROP_ENTRY(NAME, MODE, XARG, RESARG)                                                                         \
@@ -102,7 +73,7 @@ inline bool drop_params(float p, unsigned &thresh, float &scale) {
   float scale;                                                                                                       \
   SPACAP_REQUIRE(n >= 0 && drop_params(p, thresh, scale), NAME ": bad arguments (n=%ld, p=%f)", n, (double)p);      \
   if (n == 0) return SPACAP_OK;                                                                                      \
-  SPACAP_REQUIRE(XARG && out && ((reinterpret_cast<uintptr_t>(XARG) | reinterpret_cast<uintptr_t>(out)) & 15) == 0, \
+  SPACAP_REQUIRE(XARG && out && aligned16(XARG, out),                                                                \
                  NAME ": null or unaligned pointer");                                                               \
   hipLaunchKernelGGL((drop_kernel<MODE>), dim3(grid_for(n)), dim3(256), 0, spacap::as_stream(stream), XARG, RESARG,  \
                      n, thresh, scale, (unsigned long long)seed, (const unsigned long long *)seed_dev, out);         \
@@ -189,8 +160,7 @@ extern "C" int spacap_adam_flat_f32(float *p, const float *g, float *m, float *v
   SPACAP_REQUIRE(n >= 0, "spacap_adam_flat_f32: bad size");
   if (n == 0) return SPACAP_OK;
   SPACAP_REQUIRE(p && g && m && v && step, "spacap_adam_flat_f32: null pointer");
-  SPACAP_REQUIRE(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                   reinterpret_cast<uintptr_t>(v)) & 15) == 0, "spacap_adam_flat_f32: unaligned pointer");
+  SPACAP_REQUIRE(aligned16(p, g, m, v), "spacap_adam_flat_f32: unaligned pointer");
   hipLaunchKernelGGL(adam_flat_kernel, dim3(grid_for(n)), dim3(256), 0, spacap::as_stream(stream), p, g, m, v, n, lr, beta1,
                      beta2, eps, weight_decay, step, grad_scale, reinterpret_cast<const long long *>(skip_if_nonzero));
   SPACAP_CHECK_LAUNCH("spacap_adam_flat_f32");
@@ -271,7 +241,7 @@ extern "C" int spacap_sum_slabs_batched_f32(const float *const *parts, float *co
     long blocks = 0;
     for (int i = base; i < nseg && T.nseg < SLAB_SEG_MAX; ++i) {
       SPACAP_REQUIRE(nslabs[i] >= 1 && n[i] >= 0 && (n[i] & 3) == 0 && parts[i] && outs[i] &&
-                         ((reinterpret_cast<uintptr_t>(parts[i]) | reinterpret_cast<uintptr_t>(outs[i])) & 15) == 0,
+                         aligned16(parts[i], outs[i]),
                      "%s: segment %d: bad size or unaligned pointer", what, i);
       if (n[i] == 0) continue;
       SlabSeg &sg = T.seg[T.nseg++];
@@ -290,7 +260,7 @@ extern "C" int spacap_sum_slabs_batched_f32(const float *const *parts, float *co
 extern "C" int spacap_sum_slabs_f32(const float *part, int nslab, long n, float *out, spacap_stream_t stream) {
   SPACAP_REQUIRE(nslab >= 1 && n >= 0 && (n & 3) == 0, "spacap_sum_slabs_f32: bad sizes (nslab=%d, n=%ld)", nslab, n);
   if (n == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(part && out && ((reinterpret_cast<uintptr_t>(part) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+  SPACAP_REQUIRE(part && out && aligned16(part, out),
                  "spacap_sum_slabs_f32: null or unaligned pointer");
   const long n4 = n >> 2;
   hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, spacap::as_stream(stream), part, nslab, n4,
@@ -314,7 +284,7 @@ __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const float *__restrict
     const f32x4 v = *reinterpret_cast<const f32x4 *>(xr + c);
     s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
   }
-  s = spacap::wave_sum_f32(s);
+  s = spacap::wave_sum(s);
   const float nrm = sqrtf(s);
   for (int c = lane * 4; c < D; c += 256) {
     f32x4 v = *reinterpret_cast<const f32x4 *>(xr + c);
@@ -335,7 +305,7 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float *__restrict
     const f32x4 a = *reinterpret_cast<const f32x4 *>(gr + c), b = *reinterpret_cast<const f32x4 *>(yr + c);
     s += a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
   }
-  s = spacap::wave_sum_f32(s);
+  s = spacap::wave_sum(s);
   const float inv = inv_norm[r];
   for (int c = lane * 4; c < D; c += 256) {
     const f32x4 a = *reinterpret_cast<const f32x4 *>(gr + c), b = *reinterpret_cast<const f32x4 *>(yr + c);

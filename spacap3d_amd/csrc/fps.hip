@@ -29,29 +29,9 @@ namespace {
 using namespace spacap;
 struct __attribute__((aligned(16))) f32x4s { float x, y, z, w; };
 
-// v_min_f32 without the canonicalising v_max hipcc emits in front of fminf (operands are never sNaN here);
-// in IEEE mode it returns the non-NaN operand, i.e. the reference's fminf (sampling_gpu.cu:106).
-__device__ __forceinline__ float vmin_f32(float a, float b) {
-  float r;
-  asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
 __device__ __forceinline__ float sqdist(float x2, float y2, float z2, float x1, float y1, float z1) {
   const float dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;
   return dx * dx + dy * dy + dz * dz;
-}
-
-// key(k) orders candidates the way the reference's tree does; smaller key wins.
-__device__ __forceinline__ unsigned fps_key(int k, int lg) {
-  const unsigned low = (unsigned)k & ((1u << lg) - 1u);
-  const unsigned rev = lg ? (__brev(low) >> (32 - lg)) : 0u;
-  return (rev << 20) | ((unsigned)k >> lg);
-}
-__device__ __forceinline__ int fps_unkey(unsigned key, int lg) {
-  const unsigned rev = key >> 20;
-  const unsigned low = lg ? (__brev(rev) >> (32 - lg)) : 0u;
-  return (int)(((key & 0xFFFFFu) << lg) | low);
 }
 
 template <int BLOCK, int TPL>

@@ -14,39 +14,12 @@
 // Round: lanes 0..NB-1 of each wave test their wave's NB buckets (box distance vs bucket max), one ballot gives
 // the wave-uniform to-do mask; touched buckets stream their coordinates from L2 (coalesced 16-byte loads), update
 // temp in VGPRs and refresh the bucket max with a DPP reduction; the arg-max needs only the bucket maxima (SGPRs).
-// The index of the maximum is recovered as in fps.hip: min over key = (bitrev(k mod bs), k div bs) of the points
-// that hold the maximum, k being the ORIGINAL index (the reference's shared-memory tree tie-break).
+// The index of the maximum is recovered as in fps.hip: min over fps_key (common.hpp) of the points that hold the
+// maximum, k being the ORIGINAL index.
 // Each wave caches its own candidate (value, key, xyz) and recomputes it only when the bucket holding it was
 // touched; one LDS exchange + ONE barrier per round decides the winner and hands its coordinates to everyone.
-__device__ __forceinline__ unsigned fpsb_key(int k, int lg) {
-  const unsigned low = (unsigned)k & ((1u << lg) - 1u);
-  const unsigned rev = lg ? (__brev(low) >> (32 - lg)) : 0u;
-  return (rev << 20) | ((unsigned)k >> lg);
-}
-__device__ __forceinline__ int fpsb_unkey(unsigned key, int lg) {
-  const unsigned rev = key >> 20;
-  const unsigned low = lg ? (__brev(rev) >> (32 - lg)) : 0u;
-  return (int)(((key & 0xFFFFFu) << lg) | low);
-}
-// v_min_f32 without the canonicalising v_max hipcc puts in front of fminf (operands here are never sNaN);
-// IEEE mode returns the non-NaN operand, which is the reference's fminf behaviour (sampling_gpu.cu:106).
-__device__ __forceinline__ float fpsb_vmin(float a, float b) {
-  float r;
-  asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
 __device__ __forceinline__ unsigned fpsb_spread4(unsigned q) {  // bits 0..3 -> positions 0,3,6,9
   return (q & 1u) | ((q & 2u) << 2) | ((q & 4u) << 4) | ((q & 8u) << 6);
-}
-__device__ __forceinline__ float fpsb_wave_min_f32(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float fpsb_wave_max_f32(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
 }
 
 // The NB template instance launch_fps_bucket dispatches for N points: ceil(N / 4096) rounded UP to an instantiated
@@ -106,8 +79,8 @@ __global__ __launch_bounds__(1024) void fps_bucket_kernel(const float *__restric
     }
   }
   for (int c = tid; c < NCELL; c += BLOCK) s_hist[c] = 0;
-  lox = fpsb_wave_min_f32(lox); loy = fpsb_wave_min_f32(loy); loz = fpsb_wave_min_f32(loz);
-  hix = fpsb_wave_max_f32(hix); hiy = fpsb_wave_max_f32(hiy); hiz = fpsb_wave_max_f32(hiz);
+  lox = wave_min(lox); loy = wave_min(loy); loz = wave_min(loz);
+  hix = wave_max(hix); hiy = wave_max(hiy); hiz = wave_max(hiz);
   if (lane == 0) {
     s_box[wid * 6 + 0] = lox; s_box[wid * 6 + 1] = loy; s_box[wid * 6 + 2] = loz;
     s_box[wid * 6 + 3] = hix; s_box[wid * 6 + 4] = hiy; s_box[wid * 6 + 5] = hiz;
@@ -191,8 +164,8 @@ __global__ __launch_bounds__(1024) void fps_bucket_kernel(const float *__restric
       }
     }
     t[b] = tt;
-    mnx = fpsb_wave_min_f32(mnx); mny = fpsb_wave_min_f32(mny); mnz = fpsb_wave_min_f32(mnz);
-    mxx = fpsb_wave_max_f32(mxx); mxy = fpsb_wave_max_f32(mxy); mxz = fpsb_wave_max_f32(mxz);
+    mnx = wave_min(mnx); mny = wave_min(mny); mnz = wave_min(mnz);
+    mxx = wave_max(mxx); mxy = wave_max(mxy); mxz = wave_max(mxz);
     const int lm = max(max(__float_as_int(tt.x), __float_as_int(tt.y)), max(__float_as_int(tt.z), __float_as_int(tt.w)));
     gm[b] = wave_max_i32_fast(lm);
     if (lane == b) {
@@ -232,7 +205,7 @@ __global__ __launch_bounds__(1024) void fps_bucket_kernel(const float *__restric
         const f32x4 dx = x - x1, dy = y - y1, dz = z - z1;
         const f32x4 d = dx * dx + dy * dy + dz * dz;
         f32x4 tt = t[b];
-        tt.x = fpsb_vmin(d.x, tt.x); tt.y = fpsb_vmin(d.y, tt.y); tt.z = fpsb_vmin(d.z, tt.z); tt.w = fpsb_vmin(d.w, tt.w);
+        tt.x = vmin_f32(d.x, tt.x); tt.y = vmin_f32(d.y, tt.y); tt.z = vmin_f32(d.z, tt.z); tt.w = vmin_f32(d.w, tt.w);
         t[b] = tt;
         const int lm = max(max(__float_as_int(tt.x), __float_as_int(tt.y)), max(__float_as_int(tt.z), __float_as_int(tt.w)));
         gm[b] = wave_max_i32_fast(lm);
@@ -253,7 +226,7 @@ __global__ __launch_bounds__(1024) void fps_bucket_kernel(const float *__restric
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
               if (__float_as_int(t[b][u]) == wmax) {
-                const unsigned ku = fpsb_key(PERM_LDS ? (int)s_perm[slot0 + u] : (int)gperm[slot0 + u], lg);
+                const unsigned ku = fps_key(PERM_LDS ? (int)s_perm[slot0 + u] : (int)gperm[slot0 + u], lg);
                 if (ku < key) { key = ku; kslot = slot0 + u; }
               }
             }
@@ -281,7 +254,7 @@ __global__ __launch_bounds__(1024) void fps_bucket_kernel(const float *__restric
     }
     const int bw = wave_max_i32_fast(rw);
     const unsigned bk = wave_min_u32_fast(rw == bw ? rk : 0xFFFFFFFFu);
-    int old = (bw < 0) ? 0 : fpsb_unkey(bk, lg);  // every point skipped: the reference returns index 0
+    int old = (bw < 0) ? 0 : fps_unkey(bk, lg);  // every point skipped: the reference returns index 0
     old = __builtin_amdgcn_readfirstlane(old);
     x1 = xyz[old * 3 + 0]; y1 = xyz[old * 3 + 1]; z1 = xyz[old * 3 + 2];  // wave-uniform index: scalar loads
     if (tid == 0) idxs[j] = old;

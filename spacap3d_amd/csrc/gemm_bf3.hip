@@ -440,7 +440,7 @@ extern "C" int spacap_gemm_bf3_f32(const float *A, long lda, const void *Wp, con
   const char *what = "spacap_gemm_bf3_f32";
   SPACAP_REQUIRE(R >= 0 && bf3_shape(K, N) && lda >= K && ldo >= N && lda % 4 == 0, "%s: (R=%ld, K=%d, N=%d) unsupported", what, R, K, N);
   if (R == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(A && Wp && out && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(Wp) & 15) == 0,
+  SPACAP_REQUIRE(A && Wp && out && spacap::aligned16(A, Wp),
                  "%s: null / unaligned pointer", what);
   const long tiles = ((R + BM - 1) / BM) * (N / BN);
   SPACAP_REQUIRE(tiles < 2147483647L, "%s: too many tiles", what);

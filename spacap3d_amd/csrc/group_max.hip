@@ -106,7 +106,7 @@ extern "C" int spacap_group_max_f32(const float *x, long rows, int S, float *out
   if (rows == 0) return SPACAP_OK;
   SPACAP_REQUIRE(x && out && arg, "spacap_group_max_f32: null pointer");
   hipStream_t s = spacap::as_stream(stream);
-  const bool aligned = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  const bool aligned = spacap::aligned16(x);
 #define GM_CASE(SV)                                                                                   \
   if (S == SV && aligned) {                                                                           \
     const long rpb = 4 * (64 / (SV / 4)) * 4; /* rows per block per step x 4 steps */                 \
@@ -128,7 +128,7 @@ extern "C" int spacap_group_max_grad_f32(const float *grad_out, const uint8_t *a
   if (rows == 0) return SPACAP_OK;
   SPACAP_REQUIRE(grad_out && arg && grad_in, "spacap_group_max_grad_f32: null pointer");
   hipStream_t s = spacap::as_stream(stream);
-  const bool aligned = (reinterpret_cast<uintptr_t>(grad_in) & 15) == 0;
+  const bool aligned = spacap::aligned16(grad_in);
   const unsigned grid = 256 * 16;
 #define GMG_CASE(SV)                                                                                       \
   if (S == SV && aligned) {                                                                                \

@@ -25,10 +25,10 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restr
     const float *xr = x + row * D;
     float s = 0.f;
     for (int j = lane; j < D; j += 64) s += xr[j];
-    const float mu = spacap::wave_sum_f32(s) / (float)D;
+    const float mu = spacap::wave_sum(s) / (float)D;
     float q = 0.f;
     for (int j = lane; j < D; j += 64) { const float c = xr[j] - mu; q += c * c; }
-    const float var = spacap::wave_sum_f32(q) / (float)(D - 1);
+    const float var = spacap::wave_sum(q) / (float)(D - 1);
     const float r = 1.0f / (sqrtf(var) + eps);
     float *yr = y + row * D;
     for (int j = lane; j < D; j += 64) yr[j] = a[j] * ((xr[j] - mu) * r) + b[j];
@@ -58,8 +58,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float *__restr
       pa[j] += g * (xc * r);
       pb[j] += g;
     }
-    s1 = spacap::wave_sum_f32(s1);
-    s2 = spacap::wave_sum_f32(s2);
+    s1 = spacap::wave_sum(s1);
+    s2 = spacap::wave_sum(s2);
     const float sd = 1.0f / r - eps;                       // the unbiased std
     const float c2 = -(s2 * r * r) / (sd * (float)(D - 1));  // 0/0 = NaN on a constant row, as autograd gives
     const float c1 = r * s1 / (float)D;
@@ -101,12 +101,12 @@ __global__ __launch_bounds__(256) void layernorm_fwd_reg_kernel(const float *__r
     v[i] = j < D ? xr[j] : 0.f;
     if (j < D) s += v[i];
   }
-  const float mu = spacap::wave_sum_f32(s) / (float)D;
+  const float mu = spacap::wave_sum(s) / (float)D;
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i)
     if (lane + 64 * i < D) { const float c = v[i] - mu; q += c * c; }
-  const float var = spacap::wave_sum_f32(q) / (float)(D - 1);
+  const float var = spacap::wave_sum(q) / (float)(D - 1);
   const float r = 1.0f / (sqrtf(var) + eps);
   float *yr = y + row * D;
 #pragma unroll
@@ -153,8 +153,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_reg_kernel(const float *__r
       pa[i] += g[i] * (xc[i] * r);
       pb[i] += g[i];
     }
-    s1 = spacap::wave_sum_f32(s1);
-    s2 = spacap::wave_sum_f32(s2);
+    s1 = spacap::wave_sum(s1);
+    s2 = spacap::wave_sum(s2);
     const float sd = 1.0f / r - eps;
     const float c2 = -(s2 * r * r) / (sd * (float)(D - 1));
     const float c1 = r * s1 / (float)D;

@@ -71,7 +71,7 @@ __device__ __forceinline__ float ce_grad(const float *s, int C, int label, float
 
 __device__ float block_sum(float v, float *s_red) {  // 256 threads, fixed order
   const int tid = threadIdx.x;
-  v = spacap::wave_sum_f32(v);
+  v = spacap::wave_sum(v);
   __syncthreads();
   if ((tid & 63) == 0) s_red[tid >> 6] = v;
   __syncthreads();
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(DET_THREADS) void det_proposal_kernel(const DetArgs
   const float v[NPARTL] = {0.f, num_obj, num_c1, num_c2, num_hc, num_hr, num_sc, num_sr, num_sem, n_obj, n_mask, n_box};
 #pragma unroll
   for (int i = 1; i < NPARTL; ++i) {
-    const float w = spacap::wave_sum_f32(v[i]);
+    const float w = spacap::wave_sum(v[i]);
     if ((tid & 63) == 0) s_red[tid >> 6][i] = w;
   }
   __syncthreads();   // (also: every row of s_net holds its gradient numerators)
@@ -545,7 +545,7 @@ __global__ __launch_bounds__(CAP_T) void cap_rows_kernel(const float *__restrict
     if (a > m) m = a, am = v;        // first maximum per thread (ascending v)
   }
   // block arg-max with the lowest index among equal maxima (torch.argmax returns the first)
-  float wm = spacap::wave_max_f32(m);
+  float wm = spacap::wave_max(m);
   int cand = (m == wm) ? am : 0x7fffffff;
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) cand = min(cand, __shfl_xor(cand, o));
@@ -559,7 +559,7 @@ __global__ __launch_bounds__(CAP_T) void cap_rows_kernel(const float *__restrict
   __syncthreads();
   float s = 0.f;
   for (int v = tid; v < V; v += CAP_T) s += expf(x[v] - M);
-  s = spacap::wave_sum_f32(s);
+  s = spacap::wave_sum(s);
   if (lane == 0) s_f[wv] = s;
   __syncthreads();
   float S = 0.f;
@@ -582,7 +582,7 @@ __global__ __launch_bounds__(64) void cap_final_kernel(const float *__restrict__
   // one wavefront: lane l adds rows l, l + 64, ... in order, then a fixed shuffle tree (bitwise reproducible)
   float a = 0.f, g = 0.f, h = 0.f, v = 0.f;
   for (int r = threadIdx.x; r < rows; r += 64) a += rowstat[r * 4], g += rowstat[r * 4 + 1], h += rowstat[r * 4 + 2], v += rowstat[r * 4 + 3];
-  a = spacap::wave_sum_f32(a), g = spacap::wave_sum_f32(g), h = spacap::wave_sum_f32(h), v = spacap::wave_sum_f32(v);
+  a = spacap::wave_sum(a), g = spacap::wave_sum(g), h = spacap::wave_sum(h), v = spacap::wave_sum(v);
   if (threadIdx.x != 0) return;
   const float inv = 1.0f / (g + 1e-6f);
   out[0] = a * inv;

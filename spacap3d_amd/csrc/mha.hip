@@ -26,10 +26,12 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "dropout.hpp"
 #include "mfma.hpp"
 
 namespace {
 
+using namespace spacap;
 using spacap::mfma::f32x4;
 
 struct MhaArgs {
@@ -51,28 +53,13 @@ struct MhaArgs {
   int vec;                          // q / k / v rows are 16-byte aligned (bases and strides): operands by 16-byte loads
 };
 
-// Dropout keep decision of element (b, head, q, key): a counter hash (murmur3 fmix32 over the element index mixed
-// with both words of the seed), the same function in forward and backward.  The seed = host seed + device-resident
-// step counter is formed once per kernel (drop_seed): a 64-bit splitmix finaliser per element cost ~10 us of VALU time
-// in each of the three kernels of an encoder layer.
-struct DropSeed {
-  unsigned lo, hi;
-};
-__device__ __forceinline__ DropSeed drop_seed(const MhaArgs &A) {
-  const unsigned long long s = A.seed + (A.seed_dev ? *A.seed_dev * 0x9E3779B97F4A7C15ull : 0ull);
-  return DropSeed{(unsigned)s, (unsigned)(s >> 32)};
-}
+// Dropout keep decision of element (b, head, q, key): the counter hash of dropout.hpp over the flat index into p, the
+// same in forward and backward.  The seed is formed once per kernel (make_seed): a 64-bit splitmix finaliser per element
+// cost ~10 us of VALU time in each of the three kernels of an encoder layer.
 __device__ __forceinline__ bool keep_elem(const MhaArgs &A, DropSeed sd, int b, int hh, int q, int key) {
   if (A.drop_thresh == 0u) return true;
   const unsigned long long idx = (((unsigned long long)b * A.h + hh) * A.Lq + q) * (unsigned long long)A.Lk + key;
-  unsigned h = (unsigned)idx ^ sd.lo;
-  h += ((unsigned)(idx >> 32) ^ sd.hi) * 0x9E3779B1u;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h >= A.drop_thresh;
+  return hash32(idx, sd) >= A.drop_thresh;
 }
 
 // logit of (q, key) from the raw dot product: scale, optional bias, key mask (-1e9), padding (-inf)
@@ -126,7 +113,7 @@ static __device__ __forceinline__ f32x4 ldv(const float *p, int vec) {
 // ------------------------------------------------------------------------------------------------
 template <int NT, int DK>
 __global__ __launch_bounds__(256) void mha_fwd_kernel(const MhaArgs A) {
-  const DropSeed sd = drop_seed(A);
+  const DropSeed sd = make_seed(A.seed, A.seed_dev);
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.z, hh = blockIdx.y;
   const int q0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
@@ -240,7 +227,7 @@ __global__ __launch_bounds__(256) void mha_fwd_kernel(const MhaArgs A) {
 // itself): the dQ and the dK / dV halves are then independent and run as ONE launch (mha_bwd_both_*).
 template <int NT, int DK, bool PRE>
 __device__ __forceinline__ void bwd_dq_body(const MhaArgs &A, int bx) {
-  const DropSeed sd = drop_seed(A);
+  const DropSeed sd = make_seed(A.seed, A.seed_dev);
   const int lane = threadIdx.x;
   const int b = blockIdx.z, hh = blockIdx.y;
   const int q0 = bx * 16;
@@ -340,7 +327,7 @@ __global__ __launch_bounds__(64) void mha_bwd_dq_kernel(const MhaArgs A) {
 // ------------------------------------------------------------------------------------------------
 template <int DK>
 __device__ __forceinline__ void bwd_dkv_body(const MhaArgs &A, int bx) {
-  const DropSeed sd = drop_seed(A);
+  const DropSeed sd = make_seed(A.seed, A.seed_dev);
   const int lane = threadIdx.x;
   const int b = blockIdx.z, hh = blockIdx.y;
   const int key0 = bx * 16;
@@ -438,7 +425,7 @@ __global__ __launch_bounds__(64) void mha_bwd_both_kernel(const MhaArgs A, int n
 // ------------------------------------------------------------------------------------------------
 template <int NTW, int DK>  // NTW key tiles per wave, 4 waves: Lk <= 64 * NTW
 __global__ __launch_bounds__(256) void mha_fwd_split_kernel(const MhaArgs A) {
-  const DropSeed sd = drop_seed(A);
+  const DropSeed sd = make_seed(A.seed, A.seed_dev);
   __shared__ float s_m[4][16], s_l[4][16];
   __shared__ float s_o[4][16][DK + 1];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -567,7 +554,7 @@ __global__ __launch_bounds__(256) void mha_fwd_split_kernel(const MhaArgs A) {
 
 template <int NTW, int DK, bool PRE>
 __device__ __forceinline__ void bwd_dq_split_body(const MhaArgs &A, int bx) {
-  const DropSeed sd = drop_seed(A);
+  const DropSeed sd = make_seed(A.seed, A.seed_dev);
   __shared__ float s_d[4][16];
   __shared__ float s_o[4][16][DK + 1];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -680,7 +667,7 @@ __global__ __launch_bounds__(256) void mha_bwd_dq_split_kernel(const MhaArgs A) 
 // dK / dV: 16 keys per workgroup, the query tiles interleaved over the 4 waves
 template <int DK>
 __device__ __forceinline__ void bwd_dkv_split_body(const MhaArgs &A, int bx) {
-  const DropSeed sd = drop_seed(A);
+  const DropSeed sd = make_seed(A.seed, A.seed_dev);
   __shared__ float s_k[4][16][DK + 1], s_v[4][16][DK + 1];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int b = blockIdx.z, hh = blockIdx.y;
@@ -806,12 +793,11 @@ int fill_args(MhaArgs &A, const char *what, const float *q, const float *k, cons
   A.bias = bias; A.bias_sb = bias_sb; A.bias_sh = bias_sh; A.bias_sq = bias_sq;
   A.B = B; A.h = h; A.Lq = Lq; A.Lk = Lk;
   A.scale = scale;
-  A.keep_scale = 1.0f / (1.0f - dropout_p);
-  A.drop_thresh = dropout_p > 0.f ? (unsigned)fmin(4294967295.0, (double)dropout_p * 4294967296.0) : 0u;
+  drop_params(dropout_p, A.drop_thresh, A.keep_scale);
   A.seed = seed;
   A.seed_dev = reinterpret_cast<const unsigned long long *>(seed_dev);
   auto al = [](const void *p, long a, long b2, long c) {
-    return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && a % 4 == 0 && b2 % 4 == 0 && c % 4 == 0;
+    return aligned16(p) && a % 4 == 0 && b2 % 4 == 0 && c % 4 == 0;
   };
   A.vec = al(q, q_sb, q_sh, q_sl) && al(k, k_sb, k_sh, k_sl) && al(v, v_sb, v_sh, v_sl) ? 1 : 0;
   A.out = A.p_out = A.stats = nullptr;

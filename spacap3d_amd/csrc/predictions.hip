@@ -106,7 +106,7 @@ extern "C" int spacap_dense_caption_select(const uint8_t *valid, const float *ob
   SPACAP_REQUIRE(valid && obj_prob && sem_cls && bbox_corner && tokens && count && index && score && cls && corners && out_tokens &&
                      length,
                  "%s: null pointer", what);
-  SPACAP_REQUIRE((reinterpret_cast<uintptr_t>(bbox_corner) & 15) == 0 && (reinterpret_cast<uintptr_t>(corners) & 15) == 0,
+  SPACAP_REQUIRE(spacap::aligned16(bbox_corner, corners),
                  "%s: bbox_corner and corners must be 16-byte aligned", what);
   PredArgs a;
   a.valid = valid;

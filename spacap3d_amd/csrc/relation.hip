@@ -73,7 +73,7 @@ extern "C" int spacap_relation_feature_fwd_f32(const float *P, const float *V, l
   if (B == 0) return SPACAP_OK;
   SPACAP_REQUIRE(P && V && R, "spacap_relation_feature_fwd_f32: null pointer");
   SPACAP_REQUIRE(B <= 65535 && (v_sb % 4) == 0 && (v_sh % 4) == 0 && (v_sl % 4) == 0 &&
-                     (reinterpret_cast<uintptr_t>(V) & 15) == 0,
+                     spacap::aligned16(V),
                  "spacap_relation_feature_fwd_f32: V must be 16-byte aligned with strides multiple of 4");
   hipLaunchKernelGGL(relation_fwd_kernel, dim3(K, B), dim3(256), 0, spacap::as_stream(stream), P, V, v_sb, v_sh, v_sl, H,
                      K, D, R);
@@ -88,7 +88,7 @@ extern "C" int spacap_relation_feature_bwd_f32(const float *dR, const float *P, 
   if (B == 0) return SPACAP_OK;
   SPACAP_REQUIRE(dR && P && V && dP && dV, "spacap_relation_feature_bwd_f32: null pointer");
   SPACAP_REQUIRE(B <= 65535 && (v_sb % 4) == 0 && (v_sh % 4) == 0 && (v_sl % 4) == 0 &&
-                     (reinterpret_cast<uintptr_t>(V) & 15) == 0,
+                     spacap::aligned16(V),
                  "spacap_relation_feature_bwd_f32: V must be 16-byte aligned with strides multiple of 4");
   const int RPI = 256 / (H * D / 4);
   hipLaunchKernelGGL(relation_bwd_kernel, dim3((K + RPI - 1) / RPI, B), dim3(256), 0, spacap::as_stream(stream), dR, P,

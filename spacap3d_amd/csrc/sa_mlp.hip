@@ -222,8 +222,7 @@ __global__ __launch_bounds__(1024) void sa_l1_moments_finalize_kernel(const doub
   if (m < 14) {   // wave m adds moment m over the partial rows: lane l takes rows l, l + 64, .. in order, then a fixed tree
     double v = 0.0;
     for (int p = lane; p < nparts; p += 64) v += part[(size_t)p * 16 + m];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    v = spacap::wave_sum(v);
     if (lane == 0) s_mom[m] = v;
   }
   __syncthreads();
@@ -235,19 +234,12 @@ __global__ __launch_bounds__(1024) void sa_l1_moments_finalize_kernel(const doub
     const double q = w[0] * w[0] * Q[0] + w[1] * w[1] * Q[4] + w[2] * w[2] * Q[7] + w[3] * w[3] * Q[9] +
                      2.0 * (w[0] * w[1] * Q[1] + w[0] * w[2] * Q[2] + w[0] * w[3] * Q[3] + w[1] * w[2] * Q[5] + w[1] * w[3] * Q[6] +
                             w[2] * w[3] * Q[8]);
-    const double mean = sm / M;
-    double var = q / M - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float istd = (float)(1.0 / sqrt(var + (double)eps));
-    stats[tid * 4 + 0] = (float)mean;
-    stats[tid * 4 + 1] = istd;
-    stats[tid * 4 + 2] = gamma[tid] * istd;
+    const spacap::BnChannel bn = spacap::bn_channel(sm, q, M, eps);
+    stats[tid * 4 + 0] = (float)bn.mean;
+    stats[tid * 4 + 1] = bn.istd;
+    stats[tid * 4 + 2] = gamma[tid] * bn.istd;
     stats[tid * 4 + 3] = beta[tid];
-    if (running_mean) {
-      const double unbiased = M > 1.0 ? var * M / (M - 1.0) : var;
-      running_mean[tid] = (float)((1.0 - momentum) * running_mean[tid] + momentum * mean);
-      running_var[tid] = (float)((1.0 - momentum) * running_var[tid] + momentum * unbiased);
-    }
+    if (running_mean) spacap::bn_update_running(bn, M, momentum, running_mean, running_var, tid);
   }
 }
 
@@ -272,19 +264,12 @@ __global__ __launch_bounds__(1024) void sa_bn_finalize_kernel(const double *__re
   if (tid < 8 && c < C) {
     double sm = 0.0, q = 0.0;
     for (int i = 0; i < 64; ++i) sm += s[i][tid], q += s[i][tid + 8];
-    const double mean = sm / M;
-    double var = q / M - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float istd = (float)(1.0 / sqrt(var + (double)eps));
-    stats[c * 4 + 0] = (float)mean;
-    stats[c * 4 + 1] = istd;
-    stats[c * 4 + 2] = gamma[c] * istd;
+    const spacap::BnChannel bn = spacap::bn_channel(sm, q, M, eps);
+    stats[c * 4 + 0] = (float)bn.mean;
+    stats[c * 4 + 1] = bn.istd;
+    stats[c * 4 + 2] = gamma[c] * bn.istd;
     stats[c * 4 + 3] = beta[c];
-    if (running_mean) {
-      const double unbiased = M > 1.0 ? var * M / (M - 1.0) : var;
-      running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
-      running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unbiased);
-    }
+    if (running_mean) spacap::bn_update_running(bn, M, momentum, running_mean, running_var, c);
   }
 }
 
@@ -1448,7 +1433,7 @@ extern "C" int spacap_sa_l1_moments_f32(const float *feat, const float *xyz, con
                                         int Np, int N, int S, float *rel4, double *mom, spacap_stream_t stream) {
   const char *what = "spacap_sa_l1_moments_f32";
   SPACAP_REQUIRE(B >= 1 && Np >= 1 && N >= 1 && S >= 1 && S <= 255, "%s: bad sizes", what);
-  SPACAP_REQUIRE(xyz && new_xyz && idx && rel4 && mom && rdiv > 0.f && (reinterpret_cast<uintptr_t>(rel4) & 15) == 0, "%s: bad arguments", what);
+  SPACAP_REQUIRE(xyz && new_xyz && idx && rel4 && mom && rdiv > 0.f && spacap::aligned16(rel4), "%s: bad arguments", what);
   const long R = (long)B * N * S;
   hipLaunchKernelGGL(sa_l1_moments_kernel, dim3(NPART), dim3(256), 0, spacap::as_stream(stream), feat, xyz, new_xyz, idx, rdiv, Np, N, S, R,
                      rel4, mom);
@@ -1724,7 +1709,7 @@ extern "C" int spacap_sa_l3bwd_dw_f32(const float *partW, int nparts, const floa
                                       float *dW3, spacap_stream_t stream) {
   const char *what = "spacap_sa_l3bwd_dw_f32";
   SPACAP_REQUIRE(partW && coef3 && W3 && sums && dW3 && nparts >= 1 && C3 >= 1 && C2 >= 4 && C2 % 4 == 0, "%s: bad arguments", what);
-  SPACAP_REQUIRE((reinterpret_cast<uintptr_t>(partW) & 15) == 0, "%s: partW must be 16-byte aligned", what);
+  SPACAP_REQUIRE(spacap::aligned16(partW), "%s: partW must be 16-byte aligned", what);
   const long n = spacap_sa_l3bwd_part_floats(C2, C3);
   hipStream_t s = spacap::as_stream(stream);
   SPACAP_REQUIRE(C2 <= 1024 && 1024 % C2 == 0, "%s: C2=%d unsupported", what, C2);
@@ -1757,7 +1742,7 @@ extern "C" int spacap_sa_wgrad_pool_f32(const float *dym, const uint8_t *arg, in
   const char *what = "spacap_sa_wgrad_pool_f32";
   SPACAP_REQUIRE(dym && arg && coef3 && z2 && st2 && partW && R >= 1, "%s: bad arguments", what);
   SPACAP_REQUIRE(wgrad_pool_shape(C2, C3, S) && R % S == 0, "%s: (C2=%d, C3=%d, S=%d) unsupported", what, C2, C3, S);
-  SPACAP_REQUIRE((reinterpret_cast<uintptr_t>(arg) & 3) == 0 && ((reinterpret_cast<uintptr_t>(z2) | reinterpret_cast<uintptr_t>(dym)) & 15) == 0,
+  SPACAP_REQUIRE((reinterpret_cast<uintptr_t>(arg) & 3) == 0 && spacap::aligned16(z2, dym),
                  "%s: unaligned pointer (arg: 4 bytes, z2 / dym: 16 bytes)", what);
   const WPArgs a{dym, arg, coef3, z2, st2, R, partW};
   const int grid = wgrad_pool_grid(R, C2, S);

@@ -29,10 +29,12 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "dropout.hpp"
 #include "mfma.hpp"
 
 namespace {
 
+using namespace spacap;
 using namespace spacap::mfma;
 using f32x2 = float __attribute__((ext_vector_type(2)));
 
@@ -41,25 +43,6 @@ constexpr int BM = 16;        // rows per workgroup of the row kernel
 constexpr int LDT = D + 8;    // LDS row stride of a [rows][128] fp32 tile read with ds_read_b128 (conflict-free)
 
 __device__ __forceinline__ f32x2 ld2(const float *p) { return *reinterpret_cast<const f32x2 *>(p); }
-
-// ---- dropout keep mask: the counter hash of elementwise.hip (seed word per call + device-resident step counter) ----
-struct DropSeed {
-  unsigned lo, hi;
-};
-__device__ __forceinline__ DropSeed make_seed(unsigned long long seed, const unsigned long long *seed_dev) {
-  const unsigned long long s = seed + (seed_dev ? *seed_dev * 0x9E3779B97F4A7C15ull : 0ull);
-  return DropSeed{(unsigned)s, (unsigned)(s >> 32)};
-}
-__device__ __forceinline__ unsigned hash32(unsigned long long idx, DropSeed s) {
-  unsigned h = (unsigned)idx ^ s.lo;
-  h += ((unsigned)(idx >> 32) ^ s.hi) * 0x9E3779B1u;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
 
 struct TfRowsArgs {
   long R;
@@ -889,14 +872,9 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const float *__restric
     }
     logit = a * scale;
   }
-  float mx = logit;
-#pragma unroll
-  for (int o = 16; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  const float mx = wave_max<32>(logit);   // a head's 32 key lanes
   const float e = tk <= t ? __expf(logit - mx) : 0.f;
-  float sum = e;
-#pragma unroll
-  for (int o = 16; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
-  s_p[hh][tk] = e / sum;
+  s_p[hh][tk] = e / wave_sum<32>(e);
   __syncthreads();
   // thread (head, half, d): keys of its parity
   const int d = tk & 15, par = tk >> 4;
@@ -908,14 +886,6 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const float *__restric
   acc += __shfl_xor(acc, 16);
   if (par == 0) out[row * HD + hh * 16 + d] = acc;
 }
-
-inline bool drop_params(float p, unsigned &thresh, float &scale) {
-  if (!(p >= 0.f && p < 1.f)) return false;
-  thresh = p > 0.f ? (unsigned)((double)p * 4294967296.0) : 0u;
-  scale = 1.0f / (1.0f - p);
-  return true;
-}
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -933,7 +903,7 @@ extern "C" int spacap_tf_rows_f32(const spacap_tf_rows_args *a, spacap_stream_t 
   P.x_ln = a->x_ln, P.G = a->g, P.part = a->part, P.W2 = a->w2, P.bias2 = a->bias2, P.out2 = a->out2, P.N2 = a->n2;
   P.nparts = a->nparts;
   P.attn_out = a->attn_out, P.delta_out = a->delta_out, P.Lq = a->lq;
-  SPACAP_REQUIRE(!P.delta_out || (a->mode == 1 && P.N2 == 128 && P.attn_out && P.Lq >= 1 && a->R % P.Lq == 0 && al16(P.attn_out)),
+  SPACAP_REQUIRE(!P.delta_out || (a->mode == 1 && P.N2 == 128 && P.attn_out && P.Lq >= 1 && a->R % P.Lq == 0 && aligned16(P.attn_out)),
                  "%s: delta_out needs mode 1, n2 = 128, attn_out and lq dividing R", what);
   SPACAP_REQUIRE(P.nparts >= 0 && (P.nparts == 0 || P.A1), "%s: nparts = %d needs the partial sums in a1", what, P.nparts);
   const bool bwd = a->mode == 1;
@@ -947,8 +917,7 @@ extern "C" int spacap_tf_rows_f32(const spacap_tf_rows_args *a, spacap_stream_t 
     SPACAP_REQUIRE(P.x_ln && P.stats && P.x_out && P.part, "%s: backward needs x_ln, stats, x_out (dx) and part", what);
     SPACAP_REQUIRE(P.N2 == 0 || (P.N2 == 128 && P.W2 && P.out2), "%s: backward N2 must be 0 or 128", what);
   }
-  SPACAP_REQUIRE(al16(P.A1) && al16(P.W1) && al16(P.bias1) && al16(P.res) && al16(P.x_out) && al16(P.ln_a) && al16(P.ln_b) &&
-                     al16(P.n_out) && al16(P.x_ln) && al16(P.G) && al16(P.W2) && al16(P.bias2) && al16(P.out2),
+  SPACAP_REQUIRE(aligned16(P.A1, P.W1, P.bias1, P.res, P.x_out, P.ln_a, P.ln_b, P.n_out, P.x_ln, P.G, P.W2, P.bias2, P.out2),
                  "%s: pointers must be 16-byte aligned", what);
   const long tiles = (P.R + BM - 1) / BM;
   SPACAP_REQUIRE(tiles <= 2147483647L, "%s: too many rows", what);
@@ -985,7 +954,7 @@ extern "C" int spacap_tf_ffn1_f32(const float *x, const float *W, const float *b
   SPACAP_REQUIRE(R >= 0 && N >= 128 && N % 128 == 0 && drop_params(drop_p, P.thresh, P.scale), "%s: (R=%ld, N=%d, p=%f) unsupported",
                  what, R, N, (double)drop_p);
   if (R == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(x && W && h && al16(x) && al16(W) && al16(bias) && al16(h), "%s: null or unaligned pointer", what);
+  SPACAP_REQUIRE(x && W && h && aligned16(x, W, bias, h), "%s: null or unaligned pointer", what);
   P.x = x, P.W = W, P.bias = bias, P.out = h, P.R = R, P.ldx = D, P.ldw = D, P.N = N, P.KS = D;
   P.seed = seed, P.seed_dev = reinterpret_cast<const unsigned long long *>(seed_dev);
   return launch_gemm<1>(what, P, false, R, N, 1, spacap::as_stream(stream));
@@ -1001,8 +970,7 @@ extern "C" int spacap_tf_ffn_f32(int mode, const float *x, const float *Wa, cons
   SPACAP_REQUIRE((mode == 0 || mode == 1) && R >= 0 && dff >= 128 && dff % 128 == 0 && drop_params(drop_p, P.thresh, P.scale),
                  "%s: (mode=%d, R=%ld, dff=%d, p=%f) unsupported", what, mode, R, dff, (double)drop_p);
   if (R == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(x && Wa && Wb && (hid || mode == 0) && part && (mode == 0 || y) && al16(x) && al16(Wa) && al16(Wb) && al16(bias) && al16(y) &&
-                     al16(hid) && al16(part), "%s: null or unaligned pointer", what);
+  SPACAP_REQUIRE(x && Wa && Wb && (hid || mode == 0) && part && (mode == 0 || y) && aligned16(x, Wa, Wb, bias, y, hid, part), "%s: null or unaligned pointer", what);
   P.x = x, P.Wa = Wa, P.Wb = Wb, P.bias = bias, P.y = y, P.hid = hid, P.part = part, P.R = R, P.dff = dff;
   P.seed = seed, P.seed_dev = reinterpret_cast<const unsigned long long *>(seed_dev);
   const bool small = R <= 512;   // few rows: 16-row tiles, so that the launch still has a few hundred workgroups
@@ -1051,8 +1019,7 @@ extern "C" int spacap_tf_ffn_bf3_f32(int mode, const float *x, const void *piece
   SPACAP_REQUIRE((mode == 0 || mode == 1) && R >= 0 && dff >= 128 && dff % 128 == 0 && drop_params(drop_p, P.thresh, P.scale),
                  "%s: (mode=%d, R=%ld, dff=%d, p=%f) unsupported", what, mode, R, dff, (double)drop_p);
   if (R == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(x && pieces && (hid || mode == 0) && part && (mode == 0 || y) && al16(x) && al16(pieces) && al16(bias) && al16(y) && al16(hid) &&
-                     al16(part), "%s: null or unaligned pointer", what);
+  SPACAP_REQUIRE(x && pieces && (hid || mode == 0) && part && (mode == 0 || y) && aligned16(x, pieces, bias, y, hid, part), "%s: null or unaligned pointer", what);
   const size_t img = (size_t)3 * dff * D;
   const __bf16 *pc = static_cast<const __bf16 *>(pieces);
   P.x = x, P.bias = bias, P.y = y, P.hid = hid, P.part = part, P.R = R, P.dff = dff;
@@ -1074,7 +1041,7 @@ extern "C" int spacap_decode_attn_f32(const float *qkv, float *kcache, float *vc
   SPACAP_REQUIRE(R >= 0 && h == 8 && d_k == 16 && T >= 1 && T <= 32 && t >= 0 && t < T, "%s: (R=%ld, h=%d, d_k=%d, T=%d, t=%d) unsupported",
                  what, R, h, d_k, T, t);
   if (R == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(qkv && kcache && vcache && out && al16(qkv) && al16(kcache) && al16(vcache) && al16(out), "%s: null or unaligned pointer", what);
+  SPACAP_REQUIRE(qkv && kcache && vcache && out && aligned16(qkv, kcache, vcache, out), "%s: null or unaligned pointer", what);
   SPACAP_REQUIRE(R <= 2147483647L, "%s: too many sequences", what);
   hipLaunchKernelGGL(decode_attn_kernel, dim3((unsigned)R), dim3(256), 0, spacap::as_stream(stream), qkv, kcache, vcache, T, t, scale, out);
   SPACAP_CHECK_LAUNCH(what);
@@ -1234,7 +1201,7 @@ extern "C" int spacap_decode_word_f32(const float *x, const void *W, const float
   const char *what = "spacap_decode_word_f32";
   SPACAP_REQUIRE(R >= 0 && V >= 1 && ys_ld >= 1 && t_out >= 0 && t_out < ys_ld, "%s: bad sizes", what);
   if (R == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(x && W && bias && lut && pe_row && ys && x_next && workspace && al16(x) && al16(W) && al16(lut) && al16(pe_row) && al16(x_next),
+  SPACAP_REQUIRE(x && W && bias && lut && pe_row && ys && x_next && workspace && aligned16(x, W, lut, pe_row, x_next),
                  "%s: null or unaligned pointer", what);
   SPACAP_REQUIRE(R <= 16L * 2147483647L, "%s: too many sequences", what);
   const int ns = va_slices(R, V);
@@ -1269,7 +1236,7 @@ extern "C" int spacap_tf_gemm_f32(const float *a, const float *W, long R, int K,
   SPACAP_REQUIRE(R >= 0 && K >= 128 && K % 128 == 0 && N >= 128 && N % 128 == 0 && nsplit >= 1 && (K / 128) % nsplit == 0,
                  "%s: (R=%ld, K=%d, N=%d, nsplit=%d) unsupported", what, R, K, N, nsplit);
   if (R == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(a && W && out && al16(a) && al16(W) && al16(out), "%s: null or unaligned pointer", what);
+  SPACAP_REQUIRE(a && W && out && aligned16(a, W, out), "%s: null or unaligned pointer", what);
   TfGemmArgs P = {};
   P.x = a, P.W = W, P.out = out, P.R = R, P.ldx = K, P.ldw = trans_w ? K : N, P.N = N, P.KS = K / nsplit;
   return launch_gemm<0>(what, P, !trans_w, R, N, nsplit, spacap::as_stream(stream));
@@ -1280,7 +1247,7 @@ extern "C" int spacap_tf_dgrad_mask_f32(const float *g, const float *W, const fl
   const char *what = "spacap_tf_dgrad_mask_f32";
   SPACAP_REQUIRE(R >= 0 && K == 128 && N >= 128 && N % 128 == 0, "%s: (R=%ld, K=%d, N=%d) unsupported", what, R, K, N);
   if (R == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(g && W && y && out && al16(g) && al16(W) && al16(y) && al16(out), "%s: null or unaligned pointer", what);
+  SPACAP_REQUIRE(g && W && y && out && aligned16(g, W, y, out), "%s: null or unaligned pointer", what);
   TfGemmArgs P = {};
   P.x = g, P.W = W, P.y = y, P.out = out, P.R = R, P.ldx = K, P.ldw = N, P.N = N, P.KS = K, P.scale = scale;
   return launch_gemm<2>(what, P, true, R, N, 1, spacap::as_stream(stream));

@@ -13,16 +13,6 @@ using namespace spacap;
 using f32x4 = float __attribute__((ext_vector_type(4)));
 using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ unsigned fps_key(int k, int lg) {
-  const unsigned low = (unsigned)k & ((1u << lg) - 1u);
-  const unsigned rev = lg ? (__brev(low) >> (32 - lg)) : 0u;
-  return (rev << 20) | ((unsigned)k >> lg);
-}
-__device__ __forceinline__ int fps_unkey(unsigned key, int lg) {
-  const unsigned rev = key >> 20;
-  const unsigned low = lg ? (__brev(rev) >> (32 - lg)) : 0u;
-  return (int)(((key & 0xFFFFFu) << lg) | low);
-}
 __device__ __forceinline__ f32x4 sqdist4(f32x4 x, f32x4 y, f32x4 z, float x1, float y1, float z1) {
   const f32x4 dx = x - x1, dy = y - y1, dz = z - z1;
   return dx * dx + dy * dy + dz * dz;
