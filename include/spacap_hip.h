@@ -841,6 +841,39 @@ size_t spacap_decode_word_workspace_bytes(long R, int V);
 int spacap_decode_word_f32(const float *x, const void *Wp, const float *bias, long R, int V, const float *lut, float scale,
                            const float *pe_row, int64_t *ys, int ys_ld, int t_out, float *x_next, void *workspace,
                            spacap_stream_t stream);
+/* Beam-search caption decoding beside the greedy step above (the reference decodes greedily only; semantics: DESIGN.md section 7e,
+ * restated by tests/beam_search_restated.py).  R sequences keep W hypotheses each, 1 <= W <= 8 <= V; row r W + w of every
+ * per-row array is hypothesis w of sequence r.
+ * spacap_beam_topw_f32: x f32 [rows,128], Wp bf16 [3][V][128], bias f32 [V] as for spacap_decode_word_f32 (the same logit
+ * arithmetic) -> top_logp f32 [rows][W], top_word i32 [rows][W]: the W largest log-probabilities logit - logsumexp(logits) of
+ * every row and their words, log-probability descending, equal ones the smaller word first; the logits never reach HBM.
+ * workspace: device memory of spacap_beam_topw_workspace_bytes(rows, V, W) bytes. */
+size_t spacap_beam_topw_workspace_bytes(long rows, int V, int W);
+int spacap_beam_topw_f32(const float *x, const void *Wp, const float *bias, long rows, int V, int W, float *top_logp, int32_t *top_word,
+                         void *workspace, spacap_stream_t stream);
+/* spacap_decode_attn_f32 on R W rows with one indirection: row r W + w appends its k, v at position t of ITS cache rows
+ * (kcache / vcache f32 [R W, T, 128]) and reads position p < t from the rows of hypothesis anc[r][w][p] of the same sequence
+ * (anc i8 [R][W][T], entries 0..W-1), so that the caches are never reordered.  h = 8, d_k = 16, T <= 32, W <= 8. */
+int spacap_decode_attn_beam_f32(const float *qkv, float *kcache, float *vcache, const int8_t *anc, long R, int W, int h, int d_k, int T,
+                                int t, float scale, float *out, spacap_stream_t stream);
+/* One selection, after the step at position t (1 <= t < T) produced top_logp / top_word [R W][W]: hypothesis j (score_in f32,
+ * fin_in i32, len_in i32, each [R][W]; score -inf = dead) offers score + top_logp[j][i] with top_word[j][i], a finished one only
+ * (score, eos); the W best (score descending, then the smaller j, then the smaller word) become score_out / fin_out / len_out
+ * (finished = parent finished or word == eos; length = the parent's + 1 unless it was finished), anc_new[r][w][p] =
+ * anc_old[r][parent][p] for p < t and parent for p == t (i8 [R][W][T]), trace_parent i8 [T-1][R][W] and trace_word i32
+ * [T-1][R][W] at index t - 1, and -- when x_next is given -- the next input rows x_next f32 [R W,128] = lut[word] * scale +
+ * pe_row (lut f32 [V,128]).  The in and out buffers must differ. */
+int spacap_beam_step_f32(const float *top_logp, const int32_t *top_word, long R, int W, int V, int T, int t, int eos, const float *score_in,
+                         const int32_t *fin_in, const int32_t *len_in, float *score_out, int32_t *fin_out, int32_t *len_out,
+                         const int8_t *anc_old, int8_t *anc_new, int8_t *trace_parent, int32_t *trace_word, const float *lut, float scale,
+                         const float *pe_row, float *x_next, spacap_stream_t stream);
+/* The end: the winner of a sequence maximises score / length^alpha (alpha = 0: the score; ties: the smaller slot); ys i64
+ * [R][n_words] = its words by backtracking the trace (eos repeats after the first eos), best_score f32 [R] = its score.  With
+ * all_tokens i64 [R][W][n_words] also every hypothesis' words, all_scores f32 [R][W] and all_len i32 [R][W] (else NULL).
+ * Every element of every output is written. */
+int spacap_beam_finish_f32(const float *score, const int32_t *len, const int8_t *trace_parent, const int32_t *trace_word, long R, int W,
+                           int n_words, double alpha, int64_t *ys, float *best_score, int64_t *all_tokens, float *all_scores,
+                           int32_t *all_len, spacap_stream_t stream);
 /* Split-K product for the skinny feed-forward products (K = d_ff, N = 128: w_2 forward, the data gradient through w_1):
  * out[s][r][n] = sum_{k in slice s} a[r][k] Wop[k][n], Wop[k][n] = trans_w ? W[n][k] (W [N,K]) : W[k][n] (W [K,N]);
  * a [R,K], K and N multiples of 128, nsplit a divisor of K / 128 (spacap_tf_gemm_splits suggests the one that fills the

@@ -29,6 +29,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "decode_common.hpp"
 #include "dropout.hpp"
 #include "mfma.hpp"
 
@@ -36,6 +37,7 @@ namespace {
 
 using namespace spacap;
 using namespace spacap::mfma;
+using namespace spacap::decode;
 using f32x2 = float __attribute__((ext_vector_type(2)));
 
 constexpr int D = 128;        // d_model
@@ -1058,72 +1060,28 @@ extern "C" int spacap_decode_attn_f32(const float *qkv, float *kcache, float *vc
 // Arithmetic: split-bf16 (three bf16 pieces per operand, the six piece products above 2^-24 on v_mfma_f32_16x16x32_bf16:
 // fp32-equivalent logits at 6/16 of the fp32-MFMA time -- 1.6 GFLOP per word on the fp32 pipe alone is 10 us).  The weight's
 // pieces Wp bf16 [3][V][128] are made once per decoding call (spacap_gemm_bf3_split_w_f32).
-constexpr int VA_CHUNK = 64, VA_LDB = D + 8, VA_ROWS = 16;
+// (the logit tile -- row split, weight staging, the six piece products -- and the compare are decode_common.hpp: shared with beam_search.hip)
 __global__ __launch_bounds__(256) void vocab_argmax_kernel(const float *__restrict__ x, const __bf16 *__restrict__ Wp, const float *__restrict__ bias,
                                                            long R, int V, int per_slice, float *__restrict__ best_v, int *__restrict__ best_i) {
-  __shared__ __attribute__((aligned(16))) __bf16 s_w[3 * VA_CHUNK * VA_LDB];
+  __shared__ __attribute__((aligned(16))) __bf16 s_w[VA_STAGE_ELEMS];
   __shared__ float s_bv[4][VA_ROWS][17];
   __shared__ int s_bi[4][VA_ROWS][17];
-  constexpr int IMGW = VA_CHUNK * VA_LDB;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
   const long row0 = (long)blockIdx.x * VA_ROWS;
   const int ns = gridDim.y, sl = blockIdx.y;
   const int v_beg = sl * per_slice, v_end = min(V, v_beg + per_slice);
-  // the sequences' rows as the A operand, split once: a[kc][piece] = pieces of x[row0 + l15][32 kc + 8 lg .. + 7]
-  bf16x8 a[D / 32][3];
-  {
-    const float *xr = x + (size_t)min(row0 + l15, R - 1) * D + 8 * lg;
-#pragma unroll
-    for (int kc = 0; kc < D / 32; ++kc) {
-      const f32x4 lo = ld4(xr + 32 * kc), hi = ld4(xr + 32 * kc + 4);
-      // (split8 of mfma.hpp, spelled out element by element: through the function this kernel's registers are allocated differently)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float v = e < 4 ? lo[e] : hi[e - 4];
-        const __bf16 h = (__bf16)v;
-        const float r1 = v - (float)h;
-        const __bf16 m = (__bf16)r1;
-        a[kc][0][e] = h, a[kc][1][e] = m, a[kc][2][e] = (__bf16)(r1 - (float)m);
-      }
-    }
-  }
+  SPACAP_VA_SPLIT_ROWS();   // bf16x8 a[kc][piece]: the sequences' rows as the A operand, split once
   float bv[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
   int bi[4] = {v_beg, v_beg, v_beg, v_beg};
-  // staging: per piece 64 rows x 16 sixteen-byte pieces = 1 024 loads: 4 per thread and piece
-  const int c8 = tid & 15, r0 = tid >> 4;
-  const size_t wimg = (size_t)V * D;
-  bf16x8 stg[3][4];
-  auto fetch = [&](int v0) {
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int v = v0 + r0 + 16 * i;
-        stg[p][i] = *reinterpret_cast<const bf16x8 *>(Wp + p * wimg + (size_t)min(v, V - 1) * D + 8 * c8);
-      }
-  };
+  SPACAP_VA_STAGING();      // stg, fetch(v0): the next chunk of the weight pieces in registers
   fetch(v_beg < V ? v_beg : 0);
   for (int v0 = v_beg; v0 < v_end; v0 += VA_CHUNK) {
     __syncthreads();
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) *reinterpret_cast<bf16x8 *>(s_w + p * IMGW + (r0 + 16 * i) * VA_LDB + 8 * c8) = stg[p][i];
+    SPACAP_VA_STORE_STAGE();
     __syncthreads();
     if (v0 + VA_CHUNK < v_end) fetch(v0 + VA_CHUNK);
     const int v = v0 + 16 * w + l15;                    // this lane's word of the chunk
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kc = 0; kc < D / 32; ++kc) {
-      bf16x8 b[3];
-#pragma unroll
-      for (int p = 0; p < 3; ++p) b[p] = *reinterpret_cast<const bf16x8 *>(s_w + p * IMGW + (16 * w + l15) * VA_LDB + 32 * kc + 8 * lg);
-#pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        if (kc & 1) acc2 = MFMA_B(a[kc][PA[q]], b[PB[q]], acc2);
-        else acc = MFMA_B(a[kc][PA[q]], b[PB[q]], acc);
-      }
-    }
+    SPACAP_VA_TILE();                                   // acc, acc2: the 16 x 16 logits of this wave's words
     if (v < v_end) {
       const float bsv = bias[v];
 #pragma unroll
@@ -1145,13 +1103,13 @@ __global__ __launch_bounds__(256) void vocab_argmax_kernel(const float *__restri
     for (int l = 0; l < 16; ++l) {
       const float val = s_bv[ww][row][l];
       const int idx = s_bi[ww][row][l];
-      if (val > m || (val == m && idx < mi)) m = val, mi = idx;
+      if (SPACAP_FIRST_MAX(val, idx, m, mi)) m = val, mi = idx;
     }
 #pragma unroll
     for (int o = 1; o <= 2; o <<= 1) {
       const float om = __shfl_xor(m, o);
       const int oi = __shfl_xor(mi, o);
-      if (om > m || (om == m && oi < mi)) m = om, mi = oi;
+      if (SPACAP_FIRST_MAX(om, oi, m, mi)) m = om, mi = oi;
     }
     if (ww == 0 && row0 + row < R) {
       best_v[(size_t)(row0 + row) * ns + sl] = m;
@@ -1172,7 +1130,7 @@ __global__ __launch_bounds__(256) void decode_next_kernel(const float *__restric
   for (int s = 0; s < ns; ++s) {
     const float val = best_v[(size_t)r * ns + s];
     const int idx = best_i[(size_t)r * ns + s];
-    if (val > m || (val == m && idx < mi)) m = val, mi = idx;
+    if (SPACAP_FIRST_MAX(val, idx, m, mi)) m = val, mi = idx;
   }
   if (c4 == 0) ys[(size_t)r * ys_ld + t_out] = mi;
   const f32x4 e = ld4(lut + (size_t)mi * D + 4 * c4), p = ld4(pe_row + 4 * c4);
@@ -1184,16 +1142,6 @@ __global__ __launch_bounds__(256) void decode_next_kernel(const float *__restric
    -> ys i64 [R][ys_ld] column t_out = arg-max word (first maximum), and the next
    step's input rows x_next f32 [R,128] = lut[word] * scale + pe_row (lut f32 [V,128], pe_row f32 [128]).
    workspace: spacap_decode_word_workspace_bytes(R, V) bytes (the vocabulary slices' winners). */
-namespace {
-inline int va_slices(long R, int V) {
-  const long tiles = (R + VA_ROWS - 1) / VA_ROWS;
-  long ns = (4L * spacap::device_cus() + tiles - 1) / tiles;   // ~4 workgroups per CU
-  const long most = (V + VA_CHUNK - 1) / VA_CHUNK;
-  if (ns > most) ns = most;
-  if (ns > 64) ns = 64;
-  return (int)(ns < 1 ? 1 : ns);
-}
-}  // namespace
 extern "C" size_t spacap_decode_word_workspace_bytes(long R, int V) { return R > 0 && V > 0 ? (size_t)R * va_slices(R, V) * 8 : 0; }
 extern "C" int spacap_decode_word_f32(const float *x, const void *W, const float *bias, long R, int V, const float *lut, float scale,
                                       const float *pe_row, int64_t *ys, int ys_ld, int t_out, float *x_next, void *workspace,
@@ -1205,7 +1153,7 @@ extern "C" int spacap_decode_word_f32(const float *x, const void *W, const float
                  "%s: null or unaligned pointer", what);
   SPACAP_REQUIRE(R <= 16L * 2147483647L, "%s: too many sequences", what);
   const int ns = va_slices(R, V);
-  const int per = ((V + ns - 1) / ns + VA_CHUNK - 1) / VA_CHUNK * VA_CHUNK;   // whole chunks per slice
+  const int per = va_per_slice(V, ns);   // whole chunks per slice
   float *bv = static_cast<float *>(workspace);
   int *bi = reinterpret_cast<int *>(bv + (size_t)R * ns);
   hipStream_t s = spacap::as_stream(stream);

@@ -750,10 +750,26 @@ class Evaluator:
     ``predictions.dense_caption_predictions`` on the post-processing tensors and the forward's boxes, classes and captions, on
     the same stream, and stores its tensors under ``pred_count``, ``pred_index``, ``pred_score``, ``pred_cls``,
     ``pred_corners``, ``pred_tokens`` and ``pred_length`` (``predictions.to_records`` turns them into lists).  The batch
-    needs no ground-truth key."""
+    needs no ground-truth key.
 
-    def __init__(self, model, graph=True, postprocess=None, detection_ap=None, caption_eval=None, predictions=None):
+    ``beam_size`` / ``length_penalty``: set the captioner's decoding attributes (``beam_size`` > 1: beam search instead of
+    greedy decoding, the forward then also returns ``lang_cap_score``).  ``lang_cap`` keeps its shape and
+    meaning, so ``caption_eval``, ``predictions`` and ``detection_ap`` consume it unchanged."""
+
+    def __init__(self, model, graph=True, postprocess=None, detection_ap=None, caption_eval=None, predictions=None, beam_size=None,
+                 length_penalty=None):
         self.model = model
+        # decoding attributes of the captioner (transformer_captioner.TransformerDecoderModel); None leaves what it has
+        cap = getattr(model, "caption", None)
+        if beam_size is not None or length_penalty is not None:
+            if cap is None or not hasattr(cap, "beam_size"):
+                raise ValueError("Evaluator: beam_size / length_penalty need a model with a Transformer captioner")
+            if beam_size is not None:
+                if int(beam_size) < 1:
+                    raise ValueError(f"Evaluator: beam_size {beam_size} < 1")
+                cap.beam_size = int(beam_size)
+            if length_penalty is not None:
+                cap.length_penalty = float(length_penalty)
         self.post_kw = None
         for name, given in (("predictions", predictions), ("detection_ap", detection_ap), ("caption_eval", caption_eval)):
             if given is not None and postprocess is None:

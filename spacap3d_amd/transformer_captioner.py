@@ -580,12 +580,34 @@ class TransformerDecoderModel(nn.Module):
                 pred = tall_linear(F.relu(tall_linear(hid, rp[2])), rp[4])
         ep["relation_pred"] = pred
 
-    def forward_eval(self, ep, use_cache=True):
+    # Decoding attributes (not parameters, not in the state-dict): the beam width and the exponent of the length in the final
+    # ranking, read by forward_eval when its arguments are None (engine.Evaluator sets them).  beam_return_all adds every final
+    # hypothesis to the outputs; beam_generic sends every width -- 1 included -- through beam_search.beam_search (parity tests).
+    beam_size = 1
+    length_penalty = 0.0
+    beam_return_all = False
+    beam_generic = False
+    last_beam_trace = None
+
+    def forward_eval(self, ep, use_cache=True, beam_size=None, length_penalty=None):
         """Greedy decoding of B*K captions (:402-453).  The reference re-runs the 6-layer encoder AND the whole
         decoder prefix at each of the 31 steps; the encoder output does not depend on the words (computed once),
         and with ``use_cache`` the decoder keeps the keys / values of earlier positions so that each step only
         processes the newest token (16x fewer token-layer evaluations).  ``use_cache=False`` recomputes the prefix
-        as the reference does (kept for parity tests)."""
+        as the reference does (kept for parity tests).
+
+        ``beam_size`` > 1 (default: the module attribute, 1): beam search instead (the reference has none)
+        -- ``lang_cap`` (B, K, n_words) holds the winners' words (eos repeats after the first eos), ``lang_cap_score`` (B, K)
+        their summed log-probabilities, and with ``beam_return_all`` ``lang_cap_beams`` (B, K, W, n_words),
+        ``lang_cap_beam_scores`` and ``lang_cap_beam_lengths`` (B, K, W) every final hypothesis.  The winner maximises
+        score / length ** ``length_penalty``."""
+        W = int(self.beam_size if beam_size is None else beam_size)
+        alpha = float(self.length_penalty if length_penalty is None else length_penalty)
+        if W < 1:
+            raise ValueError(f"forward_eval: beam_size {W} < 1")
+        beam = W > 1 or self.beam_generic
+        if beam and not use_cache:
+            raise ValueError("forward_eval: beam search keeps key / value caches (use_cache=False is the greedy parity path)")
         obj_features = ep["aggregated_vote_features"]
         if self.token_proj is not None:
             obj_features = self.token_proj(obj_features)
@@ -623,8 +645,19 @@ class TransformerDecoderModel(nn.Module):
             indicator, dec_memory = obj_flat.unsqueeze(1), memory
         embed, pos = self.model.tgt_embed[0], self.model.tgt_embed[1]
         st = getattr(ops(), "tf_stack", None)
-        if self.early_guide and not self.training and st is not None \
-                and st.decode_supported(dec.layers, indicator.squeeze(1), MAX_DES_LEN + 1):
+        fused = self.early_guide and not self.training and st is not None \
+            and st.decode_supported(dec.layers, indicator.squeeze(1), MAX_DES_LEN + 1)
+        if beam and fused and not self.beam_generic:
+            # the greedy loop below at B K W rows: top-W log-probabilities, one selection per sequence, attention through an
+            # ancestor table (tf_layer.beam_decode, csrc/beam_search.hip)
+            self.last_beam_trace = {}       # parent int8 / word int32 (n_words, R, W): the selections, for parity tests
+            got = st.beam_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), self.word_to_idx["sos"],
+                                 self.word_to_idx["eos"], MAX_DES_LEN + 1, W, alpha, return_all=self.beam_return_all,
+                                 trace=self.last_beam_trace)
+            return self._beam_outputs(ep, B, K, *got)
+        if beam:
+            return self._beam_generic(ep, B, K, W, alpha, dec, indicator, embed, pos)
+        if fused:
             # pre-allocated key / value caches, one token per sequence and step, four launches per layer (tf_layer.greedy_decode)
             words = st.greedy_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), self.word_to_idx["sos"],
                                      MAX_DES_LEN + 1)
@@ -648,3 +681,45 @@ class TransformerDecoderModel(nn.Module):
             mask = None
         ep["lang_cap"] = ys[:, 1:].view(B, K, -1)
         return ep
+
+    def _beam_outputs(self, ep, B, K, ys, score, beams=None, scores=None, lengths=None):
+        ep["lang_cap"] = ys.view(B, K, -1)
+        ep["lang_cap_score"] = score.view(B, K)
+        if beams is not None:
+            ep["lang_cap_beams"] = beams.view(B, K, beams.shape[1], -1)
+            ep["lang_cap_beam_scores"] = scores.view(B, K, -1)
+            ep["lang_cap_beam_lengths"] = lengths.view(B, K, -1)
+        return ep
+
+    def _beam_generic(self, ep, B, K, W, alpha, dec, indicator, embed, pos):
+        """Beam search through the cached per-operator decoder (``decode_incremental``): everything the fused path does not
+        take -- late guide, other head counts, the CPU oracle backend.  Row r W + w is hypothesis w of sequence r; a selection
+        reorders the key / value caches with ``index_select``."""
+        from .beam_search import beam_search
+        R = B * K
+        ind = indicator.repeat_interleave(W, 0)
+        caches = [dict() for _ in dec.layers]
+        # (early guide: the decoder has no cross-attention and never reads the memory; late guide: it attends over the indicator)
+        cross_mem = None if self.early_guide else ind
+
+        def step_fn(s, words, parents):
+            if s == 0:
+                x_new = pos.dropout(embed(words.unsqueeze(1)) + pos.pe[:, :1])
+                mask = None
+                if self.early_guide:   # positions: 0 = object indicator, 1 = sos
+                    x_new = torch.cat((ind, x_new), dim=1)
+                    mask = subsequent_mask(2, device=words.device).expand(R * W, -1, -1)
+            else:
+                for c in caches:
+                    c["k"], c["v"] = c["k"].index_select(0, parents), c["v"].index_select(0, parents)
+                x_new = pos.dropout(embed(words.unsqueeze(1)) + pos.pe[:, s:s + 1])
+                mask = None
+            out = decode_incremental(dec, x_new, caches, memory=cross_mem, src_mask=None, mask=mask)
+            return self.model.generator(out[:, -1, :])
+
+        got = beam_search(step_fn, R, W, MAX_DES_LEN + 1, self.word_to_idx["sos"], self.word_to_idx["eos"], alpha,
+                          device=indicator.device)
+        self.last_beam_trace = {k: got[k] for k in ("parent", "word", "gap")}   # (n_words, R, W) twice, (n_words, R): for parity tests
+        if self.beam_return_all:
+            return self._beam_outputs(ep, B, K, got["ys"], got["score"], got["beams"], got["scores"], got["lengths"].to(torch.int32))
+        return self._beam_outputs(ep, B, K, got["ys"], got["score"])
