@@ -1,6 +1,11 @@
 // Matrix-core primitives shared by the gfx950 kernels of libspacap_hip.so: the vector types, the two MFMA forms the library
 // uses, 16-byte loads and stores, and the split-bf16 device -- ONE definition of the split and of the
 // order of the six piece products, which is what the "fp32-equivalent products" claim rests on.
+// The claim is held per kernel and per term by tests/test_split_bf16_terms_gpu.py: every kernel that runs this table (through
+// mfma6 or a loop of its own over PA / PB, with its own piece images and fragment reads) is given inputs on which ONE of the three
+// 2^-16 products (a0 b2, a2 b0, a1 b1) is positive in every summand, and must stay under a quarter of that term's share of
+// sum |a| |b|.  On random operands a lost 2^-16 term averages out of a max-norm; there it cannot.  A kernel that gains a copy of
+// the loop gains a probe there (tests/split_bf16_restated.py: CASES).
 // Everything here is a type, a constant, a macro or a __device__ __forceinline__ function; users say
 // `using namespace spacap::mfma;` inside their own namespace.
 #pragma once
