@@ -13,13 +13,6 @@ void set_error(const char *fmt, ...);
 
 inline hipStream_t as_stream(spacap_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
-// Process-wide launch state, each defined ONCE in sa_mlp.hip: the CUs a caller asked the persistent grids to leave to
-// side-stream work (spacap_sa_reserve_cus), the device's CU count, and the library's one environment switch
-// (SPACAP_SA_F32MFMA=1: fp32-MFMA kernels instead of the split-bf16 ones)
-int sa_reserved_cus();
-int device_cus();
-bool sa_f32_mfma_only();
-
 // Raises a kernel's dynamic-LDS limit on the CURRENT device.  `done` is the call site's own bit mask of devices that already
 // have it (a function attribute is per device: a process that moves to another GPU must set it there too).
 inline hipError_t allow_dynamic_lds(const void *fn, int bytes, unsigned long long &done) {

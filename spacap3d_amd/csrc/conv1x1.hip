@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "launch.hpp"
 #include "mfma.hpp"
 
 namespace {

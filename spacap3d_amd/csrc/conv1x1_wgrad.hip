@@ -10,6 +10,7 @@
 // (contiguous along n), each (scene, point range) slab accumulates a 128 x 128 block by MFMA and writes a partial
 // result; the caller adds the slabs in order (spacap_sum_slabs_f32).
 #include "common.hpp"
+#include "launch.hpp"
 #include "mfma.hpp"
 
 namespace {

@@ -10,6 +10,7 @@
 // `using namespace spacap::mfma;` inside their own namespace; the macros name the caller's variables as listed with each.
 #pragma once
 #include "common.hpp"
+#include "launch.hpp"
 #include "mfma.hpp"
 
 namespace spacap::decode {

@@ -22,6 +22,7 @@
 // Epilogues: bias + ReLU (forward); none (data gradient: the consumer masks).  The weight gradient runs on the Linear layers'
 // split-bf16 kernel (csrc/linear_grad.hip); spacap_gemm_bf3_wgrad_slabs sizes its row slabs for the relation head.
 #include "common.hpp"
+#include "launch.hpp"
 #include "mfma.hpp"
 
 namespace {

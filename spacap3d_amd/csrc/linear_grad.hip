@@ -4,6 +4,7 @@
 // Callers: the Linear autograd functions, the fused Transformer layer and the end-of-backward flush of the Python package.
 // Built with -ffp-contract=fast (csrc/Makefile: CONTRACT_FAST), as these kernels always were.
 #include "common.hpp"
+#include "launch.hpp"
 #include "mfma.hpp"
 
 namespace {

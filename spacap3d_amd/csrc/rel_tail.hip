@@ -2,12 +2,12 @@
 //
 // Relation head, layers 2 and 3 (models/transformer_captioner.py:319-326, 392-397) on R = B*K*K pair rows:
 //   hid2 = relu(hid1 W2^T + b2) [R,128],  pred = hid2 W3^T + b3 [R,NO3 = 9]
-// Forward: sa_mid_fwd_kernel<128, 2, TAIL> in sa_mlp.hip (one pass: read hid1, write hid2 and pred; the composition of a BLAS GEMM,
+// Forward: sa_mid_fwd_kernel<128, 2, TAIL> in sa_fwd.hip (one pass: read hid1, write hid2 and pred; the composition of a BLAS GEMM,
 // a ReLU pass and a second GEMM moves 5x the bytes).  Backward, first stage (this kernel): one streaming pass over
 // hid2 that produces dz2 = (dpred W3) * (hid2 > 0) and per-workgroup partial sums of dW3 = dpred^T hid2,
 // db2 = sum dz2 and db3 = sum dpred -- replacing a GEMM, a transposed GEMM, a masking pass and two column sums, each
 // a full pass over a 268 MB tensor.  dhid1 = dz2 W2 and dW2 = dz2^T hid1 stay BLAS GEMMs (MFMA-bound).
-// The forward's entry point, spacap_rel_tail_fwd_f32, sits beside the sa_mid_fwd_kernel template in sa_mlp.hip.
+// The forward's entry point, spacap_rel_tail_fwd_f32, sits beside the sa_mid_fwd_kernel template in sa_fwd.hip.
 #include "common.hpp"
 #include "mfma.hpp"
 

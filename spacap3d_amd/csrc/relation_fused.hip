@@ -24,6 +24,7 @@
 #include <atomic>
 
 #include "common.hpp"
+#include "launch.hpp"
 #include "mfma.hpp"
 
 namespace {
@@ -447,9 +448,9 @@ constexpr size_t BWD_LDS = (size_t)2 * 3 * IMGT * 2 + (size_t)(TR * LDT + H * TR
 static std::atomic<int> g_rel_leave{0};
 inline int grid_size(int B, int K, int per_cu) {
   const long units = (long)B * (K / TJ) * (K / TI);
-  // (with two workgroups per CU the dispatcher needs slack beyond the occupied CUs themselves: sa_mlp.hip, fwd_resident)
+  // (with two workgroups per CU the dispatcher needs slack beyond the occupied CUs themselves: launch.hpp, fwd_cus_left_free)
   const int extra = g_rel_leave.load(std::memory_order_relaxed);   // CUs left to a stream that runs beside the head (below)
-  const long g = (long)per_cu * std::max(1, spacap::device_cus() - extra - spacap::sa_reserved_cus() * (per_cu > 1 ? 3 : 1));
+  const long g = (long)per_cu * std::max(1, spacap::device_cus() - extra - spacap::launch::fwd_cus_left_free(per_cu));
   return (int)std::min(units, g);
 }
 // dU slots: the largest number of workgroups whose ranges meet one key block

@@ -1,5 +1,5 @@
-// Streaming split-bf16 ("bf16 x 3") shared-MLP kernels; included by sa_mlp.hip (uses its MFMA_BF16 and NPART, and
-// ld4, f32x4, split3 and the product order PA / PB of mfma.hpp).
+// Streaming split-bf16 ("bf16 x 3") shared-MLP kernels; included by sa_fwd.hip (uses MFMA_BF16, NPART and
+// dpp_xor1 / dpp_xor2 of sa_common.hpp, and ld4, f32x4, split3 and the product order PA / PB of mfma.hpp).
 //
 // Layer:  z_out[r, :] = relu(bn(z_in[r, :])) W^T  + per-channel sum / sum of squares of z_out (pointnet2/pytorch_utils.py:
 // Conv2d -> BatchNorm2d -> ReLU chains built by SharedMLP, lib/pointnet2/pointnet2_modules.py:142-152).
@@ -21,13 +21,6 @@
       "a18", "a19", "a20", "a21", "a22", "a23", "a24", "a25", "a26", "a27", "a28", "a29", "a30", "a31"
 // nothing of the compiler's may live in the landing registers across this point
 #define SPACAP_LANDING_FENCE() asm volatile("" ::: SPACAP_ACLOB)
-
-__device__ __forceinline__ float dpp_xor1(float v) {   // value of lane ^ 1 (quad_perm [1, 0, 3, 2])
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_xor2(float v) {   // value of lane ^ 2 (quad_perm [2, 3, 0, 1])
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-}
 
 // POOL: the kernel also emits, per sub-group of min(S, 32) consecutive rows and per output channel, the two best candidates for
 // the max-pool that follows this layer (pointnet2_modules.py:259 F.max_pool2d over the nsample axis of relu(bn(z))):

@@ -1,5 +1,5 @@
-// Streaming split-bf16 data-gradient kernel of the shared MLP; included by sa_mlp.hip after sa_bf3.inc (uses ld4, f32x4, f32x16,
-// bf16x8, bf16x4, split3, MFMA_BF16, NPART, dpp_xor1 / dpp_xor2).
+// Streaming split-bf16 data-gradient kernel of the shared MLP; included by sa_bwd.hip (uses ld4, f32x4, bf16x8, bf16x4, split3 of
+// mfma.hpp and f32x16, MFMA_BF16, NPART, dpp_xor1 / dpp_xor2 of sa_common.hpp).
 //
 //   dz_k[r, c]   = g[c] d[r, c] + k0[c] - k1[c] z_k[r, c]          BatchNorm backward of layer k (coef from sa_bwd_finalize)
 //                  d = dy[r, c] (dense) or (arg[r / S, c] == r % S ? dy[r / S, c] : 0) (the max-pool's gradient)

@@ -1,5 +1,5 @@
-// Weight gradient of the POOLED last layer of a shared MLP from its INPUT pre-activation z2 alone; included by sa_mlp.hip (uses its
-// helpers: ld4, st4, f32x4, MFMA16, NPART).
+// Weight gradient of the POOLED last layer of a shared MLP from its INPUT pre-activation z2 alone; included by sa_bwd.hip (uses
+// ld4, st4, f32x4, MFMA16 of mfma.hpp and NPART).
 //
 // Reference: the autograd backward of  Conv2d 1x1 -> BatchNorm2d -> ReLU -> max_pool2d  (lib/pointnet2/pytorch_utils.py:11-36,
 // lib/pointnet2/pointnet2_modules.py:256-259).  With a2 = relu(bn(z2)) [R, C2] the layer's input, z3 = a2 W3^T its

@@ -129,7 +129,7 @@ class Pointnet2Backbone(nn.Module):
         side.wait_stream(torch.cuda.current_stream(dev))
         levels = []
         # the chain holds one CU per scene while the first SA modules' layer kernels run beside it: they size their
-        # persistent grids to the rest of the chip (csrc/sa_mlp.hip: spacap_sa_reserve_cus; cheap, idempotent)
+        # persistent grids to the rest of the chip (csrc/launch.hpp; spacap_sa_reserve_cus: cheap, idempotent)
         from ._native import check, lib
         check(lib.spacap_sa_reserve_cus(min(64, int(xyz.shape[0]))), "spacap_sa_reserve_cus")
         with torch.cuda.stream(side), torch.no_grad():

@@ -105,7 +105,7 @@ class Trainer:
         if self.side_stream is None:
             self.side_stream = _role_stream(pc.device, "side")
             # the sampling chain holds one CU per scene while the backbone's forward runs beside it: the forward layer
-            # kernels size their persistent grids to the rest of the chip (csrc/sa_mlp.hip: spacap_sa_reserve_cus)
+            # kernels size their persistent grids to the rest of the chip (csrc/launch.hpp; spacap_sa_reserve_cus)
             from ._native import check, lib
             check(lib.spacap_sa_reserve_cus(min(64, int(pc.shape[0]))), "spacap_sa_reserve_cus")
         cur = torch.cuda.current_stream(pc.device)

@@ -321,7 +321,7 @@ def conv1x1(x, conv):
 class RelationTail(Function):
     """pred = W3 relu(W2 hid1 + b2) + b3 on the B*K*K pair rows of the relation head
     (models/transformer_captioner.py:319-326, 392-397; hid1 = the first layer's ReLU output, 524 288 x 128 at the
-    benchmark shape).  Forward: ONE kernel reads hid1 and writes hid2 and pred (csrc/sa_mlp.hip: sa_mid_fwd_kernel, TAIL).
+    benchmark shape).  Forward: ONE kernel reads hid1 and writes hid2 and pred (csrc/sa_fwd.hip: sa_mid_fwd_kernel, TAIL).
     Backward: one streaming kernel gives dz2 = (dpred W3) * (hid2 > 0) and the partial sums of dW3, db2, db3
     (csrc/rel_tail.hip: rel_tail_bwd_kernel); dhid1 = dz2 W2 and dW2 = dz2^T hid1 are MFMA-bound BLAS GEMMs (the latter cut into 64 row
     slabs: the BLAS heuristics do not split that reduction)."""

@@ -2,7 +2,7 @@
 
 One autograd op for what the reference runs per SA module as QueryAndGroup -> SharedMLP -> max_pool2d
 (lib/pointnet2/pointnet2_modules.py:241-259; SharedMLP = [Conv2d 1x1 -> BatchNorm2d -> ReLU] x 3,
-lib/pointnet2/pytorch_utils.py:11-36).  See ``csrc/sa_mlp.hip`` for the kernels and the data flow.
+lib/pointnet2/pytorch_utils.py:11-36).  See ``csrc/sa_common.hpp`` for the data flow, ``csrc/sa_fwd.hip`` / ``sa_bwd.hip`` / ``sa_rows.hip`` for the kernels.
 The grouping indices come from ``ball_query`` as before; eval mode and MLP shapes without kernels keep using
 the per-operator path (``QueryAndGroup`` + ``SharedMLP``), which is also HIP.
 """
@@ -16,7 +16,7 @@ from ._native import check, lib, sum_slabs
 # SA1-shaped modules (no point features, 64 -> 64 -> ...): do not store the first layer's pre-activation (see _SAMLP.forward)
 RECOMPUTE_Z1 = True
 # ... and take that layer's BatchNorm statistics from the first and second moments of the rows' four inputs (z1 is linear in
-# them): 14 sums per row, one thread per row, instead of 2 x 64 sums with 16 threads per row (csrc/sa_mlp.hip:
+# them): 14 sums per row, one thread per row, instead of 2 x 64 sums with 16 threads per row (csrc/sa_fwd.hip:
 # sa_l1_moments_kernel; 87 -> ~20 us at SA1).  The statistics differ from the summed-z1 form by rounding only (~1e-7 relative).
 L1_MOMENTS = True
 # pooled last layer: its WEIGHT gradient from z2 alone (csrc/sa_l3bwd.inc: sa_wgrad_pool_kernel -- the sparse
@@ -112,7 +112,7 @@ class _SAMLP(Function):
             part = torch.empty(nparts * 2 * max(C1, C2, C3), dtype=torch.float64, device=dev)
             stats = [torch.empty(c, 4, **f32) for c in (C1, C2, C3)]
             # SA1 (no point features, 64 -> 64): z1 never exists in HBM; the statistics pass leaves the rows' four inputs
-            # (16 bytes per row) and every later pass rebuilds z1 from them (csrc/sa_mlp.hip: L1In)
+            # (16 bytes per row) and every later pass rebuilds z1 from them (csrc/sa_common.hpp: L1In)
             recompute = RECOMPUTE_Z1 and Y is None and C1 == 64 and C2 == 64 and not (xyz.requires_grad or new_xyz.requires_grad)
             has_feat = int(feat is not None)
             z1 = torch.empty(R, 4 if recompute else C1, **f32)
@@ -253,7 +253,7 @@ class _SAMLP(Function):
             has_feat = int(feat is not None)
             fuse_l1 = (not ctx.has_Y) and (not ctx.need_xyz) and C1 == 64 and C2 == 64
             # SA1 with the rebuilt first layer: the layer's weight gradient rides the data-gradient kernel (one read of dy2 / z2
-            # instead of two, one launch fewer: csrc/sa_mlp.hip, sa_dgrad_kernel<.., WG>)
+            # instead of two, one launch fewer: csrc/sa_bwd.hip, sa_dgrad_kernel<.., WG>)
             fuse_w2 = fuse_l1 and ctx.recompute and FUSE_L2_WGRAD
             if fuse_w2:
                 pw = torch.empty(int(lib.spacap_sa_dgrad_wgrad_l1in_slabs(R)), C2, C1, **f32)
@@ -269,7 +269,7 @@ class _SAMLP(Function):
                 dW2 = sum_slabs(pw, deferrable=True)
             if fuse_l1:
                 # SA1: the first layer's weight gradient comes out of this kernel's epilogue as three sums
-                # (csrc/sa_mlp.hip, L1Args); dy1 is never written and the first-layer backward pass is skipped
+                # (csrc/sa_bwd.hip, L1Args); dy1 is never written and the first-layer backward pass is skipped
                 pl1 = torch.empty(nparts, C1 * 8 + 4, **f32)
                 if fuse_w2:
                     check(lib.spacap_sa_dgrad_wgrad_l1in_f32(dy2.data_ptr(), z2.data_ptr(), coef[1].data_ptr(), W2.data_ptr(),

@@ -12,11 +12,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="no hipcc")
 def test_compiler_never_touches_the_landing_registers_of_the_streaming_kernels():
     """csrc/sa_bf3.inc / sa_bf3_dgrad.inc prefetch rows into AGPRs a0..a63 through inline asm, invisibly to the register
-    allocator; tools/check_landing_regs.py compiles sa_mlp.hip to assembly and fails on any compiler-generated use."""
+    allocator; tools/check_landing_regs.py compiles the two units that include them (sa_fwd.hip, sa_bwd.hip) to assembly and fails
+    on any compiler-generated use.  The total pins the set of kernels under the check: 6 instantiations of sa_mid_fwd_bf3s_kernel
+    in sa_fwd and 4 of sa_dgrad_bf3s_kernel in sa_bwd; one that silently left it would pass the other two assertions."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_landing_regs.py")], capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     assert " 0 unsafe uses" in r.stdout
+    assert "sa_fwd: 6 streaming" in r.stdout and "sa_bwd: 4 streaming" in r.stdout and "total: 10 streaming kernels checked" in r.stdout, r.stdout
 
 
 def test_landing_register_checker_flags_planted_violations():

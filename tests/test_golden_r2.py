@@ -1,6 +1,6 @@
 """Round-2 golden vectors (tests/golden/make_fixtures_r2.py: the reference's own Python run in the build container):
 
-  * the reference's ``PointnetSAModuleVotes`` at the MLP shapes the FUSED shared-MLP kernels (csrc/sa_mlp.hip) cover,
+  * the reference's ``PointnetSAModuleVotes`` at the MLP shapes the FUSED shared-MLP kernels (csrc/sa_fwd.hip, sa_bwd.hip) cover,
     incl. the ``Y = F W1[:, 3:]`` first-layer path at 64 output channels with 7 and 132 input channels (BASELINE
     configs 3 and 4) -- on the GPU leg the test asserts that the fused path is the one that ran;
   * full training steps with input_feature_dim 7 (cfg3) and 132 (cfg4);

@@ -370,3 +370,43 @@ def test_pooled_layer_batchnorm_sums_from_the_kept_argmax_values(G, S, C):
     d2, p2 = run(None, zm2.data_ptr())                       # zmax alone (the z3-free path): equal on the channels with a weight
     pv0, pv2 = p0.view(nparts, 2, C), p2.view(nparts, 2, C)
     assert torch.equal(d0, d2) and torch.equal(pv0[:, :, live], pv2[:, :, live])
+
+
+def test_persistent_grid_counts_leave_the_reserved_cus_out():
+    """The grid-sizing policy of the persistent kernels (csrc/launch.hpp), read through the entry points that report a grid's
+    size; host calls only, no launch.  With n CUs reserved (spacap_sa_reserve_cus) a grid of `per` workgroups per CU shrinks from
+    per * cus to per * (cus - f n): f = 1 for the backward grids, and for the relation head's forward-side grid f = 3 with several
+    workgroups per CU (the dispatcher needs slack beyond the occupied CUs themselves), 1 with one.  A count that is no multiple
+    of the CU count at n = 0 sits at a cap (the partial-row count, the 16 MB cap on partials) and says nothing about the policy:
+    at most one of the eight may."""
+    from spacap3d_amd._native import check, lib
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    R = 1 << 22
+    counts = {}
+    for ck, cp, pooled in [(64, 64, 0), (128, 128, 0), (128, 64, 1), (128, 128, 1)]:
+        counts["wgrad_slabs(%d, %d, %d)" % (ck, cp, pooled)] = (lambda ck=ck, cp=cp, pooled=pooled: lib.spacap_sa_wgrad_slabs(R, ck, cp, pooled), False)
+    counts["dgrad_wgrad_l1in_slabs"] = (lambda: lib.spacap_sa_dgrad_wgrad_l1in_slabs(R), False)
+    for c2, c3, S in [(64, 128, 64), (128, 128, 32)]:
+        counts["wgrad_pool_parts(%d, %d, %d)" % (c2, c3, S)] = (lambda c2=c2, c3=c3, S=S: lib.spacap_sa_wgrad_pool_parts(R, c2, c3, S), False)
+    counts["relation_fused_nparts"] = (lambda: lib.spacap_relation_fused_nparts(64, 256), True)   # 64 * 32 * 32 tiles: never binds
+    assert len(counts) == 8
+    seen = {}
+    try:
+        for n in (0, 8, 24, 64):
+            check(lib.spacap_sa_reserve_cus(n), "spacap_sa_reserve_cus")
+            for name, (fn, _) in counts.items():
+                seen[name, n] = int(fn())
+    finally:
+        check(lib.spacap_sa_reserve_cus(0), "spacap_sa_reserve_cus")
+    skipped = []
+    for name, (_, fwd) in counts.items():
+        c0 = seen[name, 0]
+        print(name, [seen[name, n] for n in (0, 8, 24, 64)])
+        if c0 < cus or c0 % cus:
+            skipped.append(name)
+            continue
+        per = c0 // cus
+        f = (3 if per > 1 else 1) if fwd else 1
+        for n in (8, 24, 64):
+            assert seen[name, n] == per * (cus - f * n), (name, n, seen[name, n], per, cus)
+    assert len(skipped) <= 1, skipped

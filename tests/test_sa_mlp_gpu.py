@@ -1,4 +1,4 @@
-"""The fused point-major SA shared-MLP (spacap3d_amd/sa_mlp.py, csrc/sa_mlp.hip) against the per-operator path
+"""The fused point-major SA shared-MLP (spacap3d_amd/sa_mlp.py, csrc/sa_fwd.hip / sa_bwd.hip / sa_rows.hip) against the per-operator path
 (QueryAndGroup -> Conv2d 1x1 -> BN -> ReLU -> max over samples: the reference's own structure,
 lib/pointnet2/pointnet2_modules.py:241-259) evaluated in float64 on the CPU with torch, on identical inputs and
 grouping indices.  Tolerance: fp32 re-association (the GEMMs run on the matrix cores with a different summation
@@ -386,7 +386,7 @@ def test_pooled_layer_weight_gradient_from_z2_matches_the_dense_kernel(Cf, mlp, 
 @pytest.mark.parametrize("C,npoint,nsample,n,B", [(1, 512, 64, 6000, 2), (0, 200, 32, 3000, 2), (1, 77, 16, 1000, 3), (1, 2048, 64, 40000, 2)])
 def test_second_layer_weight_gradient_from_the_data_gradient_pass(C, npoint, nsample, n, B, monkeypatch):
     """sa_mlp.FUSE_L2_WGRAD (SA1-shaped modules with the rebuilt first layer): dW2 = dz2^T relu(bn(z1)) accumulated by the
-    data-gradient kernel from the tile it already holds (csrc/sa_mlp.hip: sa_dgrad_kernel<.., WG>) against the separate
+    data-gradient kernel from the tile it already holds (csrc/sa_bwd.hip: sa_dgrad_kernel<.., WG>) against the separate
     weight-gradient kernel (lib/pointnet2/pytorch_utils.py:11-36; autograd backward of the second Conv2d).  Everything but dW2
     comes from the same arithmetic: bit-identical; dW2 agrees at fp32 rounding level (row counts that are not multiples of the
     64-row tile included)."""

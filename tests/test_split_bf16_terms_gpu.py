@@ -218,7 +218,7 @@ def _identity_stats(C):
 def site_sa_forward(q):
     """relu(bn(.)) with identity statistics on a non-negative operand is the operand itself.  Of the four shapes of
     spacap_sa_mid_fwd_f32 only three reach csrc/sa_bf3.inc: (64, 64) has Cout % 128 != 0 and dispatches to the fp32-MFMA layer
-    kernel (sa_mlp.hip); it is kept because the entry accepts it and it must meet the same bar, but it probes no split-bf16 loop."""
+    kernel (sa_fwd.hip); it is kept because the entry accepts it and it must meet the same bar, but it probes no split-bf16 loop."""
     lib, check, st = _lib()
     nparts = int(lib.spacap_sa_nparts())
     out = []

@@ -287,7 +287,7 @@ def fps(B, N, m, dev):
 
 def sa_dgrad_wgrad_l1in(B, N, S, dev, label):
     """SA1 layer 2 backward as the step runs it since round 6: data gradient + BN sums + the first layer's three sums + the
-    layer's own weight gradient from ONE read of dy2 / z2 (csrc/sa_mlp.hip, sa_dgrad_kernel<.., L1, WG>)."""
+    layer's own weight gradient from ONE read of dy2 / z2 (csrc/sa_bwd.hip, sa_dgrad_kernel<.., L1, WG>)."""
     R = B * N * S
     dy, zk, rel4 = _rand(R, 64, dev=dev), _rand(R, 64, dev=dev), _rand(R, 4, dev=dev)
     coef, stp, W2, W1 = _stats(64, dev), _stats(64, dev), _rand(64, 64, dev=dev) * 0.1, _rand(64, 4, dev=dev)
