@@ -54,6 +54,8 @@ class HipBackend:
         self.caption_prep = _cp.caption_prep
         from . import tf_layer as _tf
         self.tf_stack = _tf
+        from . import caption_decode as _cd
+        self.caption_decode = _cd
         from . import sa_mlp as _sa
         self.sa_mlp_train = _sa.sa_mlp_train
         self.sa_mlp_eval = _sa.sa_mlp_eval

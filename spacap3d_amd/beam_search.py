@@ -1,4 +1,4 @@
-"""Beam search over any step function: the generic path beside ``tf_layer.beam_decode`` (late guide, other head counts,
+"""Beam search over any step function: the generic path beside ``caption_decode.beam_decode`` (late guide, other head counts,
 the CPU oracle backend).  The reference decodes greedily only (models/transformer_captioner.py:402-453); the semantics are
 the project's own and ``tests/beam_search_restated.py`` restates them:
 

@@ -17,10 +17,14 @@
 //                         dx = LayerNorm'(dn) + addend  (stored; per-workgroup partials of the LayerNorm parameter sums)
 //                         dy = dropout'(dx)             (stored: gradient of the sub-layer output in front of the residual)
 //                         out2 = dy W2                  (optional GEMM, N2 = 128: through the output projection)
-//   tf_ffn1_kernel:       h = dropout(relu(n W_1^T + b_1))   [R, d_ff]   (weights stationary, 64 x 128 tiles)
+//   tf_gemm_kernel<EPI>:  weights stationary, 64 x 128 tiles: partial sums over slices of k for the row kernel (EPI 0),
+//                         h = dropout(relu(n W_1^T + b_1)) [R, d_ff] (EPI 1) and its backward mask (EPI 2)
+//   tf_ffn_kernel, tf_ffn_bf3_kernel (+ tf_ffn_split_kernel): the feed-forward block as ONE launch per direction, on fp32 MFMA
+//                         or, for tall inputs, on split-bf16 products with pre-split weight images
+// Kernels first, the C entry points after them.  The same kernels with dropout off run the caption decoders' layers
+// (caption_decode.hip holds what only decoding needs).
 //
-// The feed-forward hidden layer's backward mask / data gradient is spacap_linear_dgrad_mask_f32 (linear_grad.hip), the
-// weight gradients are the batched kernel of linear_grad.hip (deferred to the end of the backward pass).
+// The weight gradients are the batched kernel of linear_grad.hip (deferred to the end of the backward pass).
 //
 // Arithmetic: v_mfma_f32_16x16x4_f32 (fp32 in, fp32 accumulate: bit-for-bit an fp32 fma chain), computed transposed
 // (weights as the A operand) so that a lane ends up with consecutive columns of one row.  Operands reach the
@@ -29,7 +33,6 @@
 #include <math.h>
 
 #include "common.hpp"
-#include "decode_common.hpp"
 #include "dropout.hpp"
 #include "mfma.hpp"
 
@@ -37,7 +40,6 @@ namespace {
 
 using namespace spacap;
 using namespace spacap::mfma;
-using namespace spacap::decode;
 using f32x2 = float __attribute__((ext_vector_type(2)));
 
 constexpr int D = 128;        // d_model
@@ -847,46 +849,16 @@ __global__ __launch_bounds__(256) void tf_ffn_split_kernel(const FfSplitTable T)
   }
 }
 
-// One greedy-decoding step of self-attention over a key / value cache (models/transformer_captioner.py:402-453: the
-// reference re-runs the whole decoder prefix for every new word; with pre-norm layers and a causal mask the newest row of
-// that recomputation equals this incremental step).  One workgroup per sequence: the new token's k, v (from its packed
-// q|k|v row) are appended at position t of the caches [R][T][h*16], thread (head, key) forms one logit, a 32-lane softmax
-// per head, then thread (head, d) accumulates sum_key p[key] v[key][d] over coalesced 64-byte reads.  h = 8, d_k = 16, T <= 32.
-__global__ __launch_bounds__(256) void decode_attn_kernel(const float *__restrict__ qkv, float *__restrict__ kc,
-                                                          float *__restrict__ vc, int T, int t, float scale,
-                                                          float *__restrict__ out) {
-  constexpr int HD = 128;
-  __shared__ float s_p[8][32];
-  const int tid = threadIdx.x, hh = tid >> 5, tk = tid & 31;
-  const size_t row = blockIdx.x;
-  const float *me = qkv + row * 3 * HD;
-  float *kr = kc + row * (size_t)T * HD, *vr = vc + row * (size_t)T * HD;
-  if (tid < 32) st4(kr + (size_t)t * HD + tid * 4, ld4(me + HD + tid * 4));
-  else if (tid < 64) st4(vr + (size_t)t * HD + (tid - 32) * 4, ld4(me + 2 * HD + (tid - 32) * 4));
-  float logit = -INFINITY;
-  if (tk <= t) {
-    const float *kp = tk == t ? me + HD + hh * 16 : kr + (size_t)tk * HD + hh * 16;   // (position t: straight from the row)
-    float a = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 kv = ld4(kp + 4 * q), qv = ld4(me + hh * 16 + 4 * q);
-      a += qv[0] * kv[0] + qv[1] * kv[1] + qv[2] * kv[2] + qv[3] * kv[3];
-    }
-    logit = a * scale;
-  }
-  const float mx = wave_max<32>(logit);   // a head's 32 key lanes
-  const float e = tk <= t ? __expf(logit - mx) : 0.f;
-  s_p[hh][tk] = e / wave_sum<32>(e);
-  __syncthreads();
-  // thread (head, half, d): keys of its parity
-  const int d = tk & 15, par = tk >> 4;
-  float acc = 0.f;
-  for (int k2 = par; k2 <= t; k2 += 2) {
-    const float v = k2 == t ? me[2 * HD + hh * 16 + d] : vr[(size_t)k2 * HD + hh * 16 + d];
-    acc += s_p[hh][k2] * v;
-  }
-  acc += __shfl_xor(acc, 16);
-  if (par == 0) out[row * HD + hh * 16 + d] = acc;
+// the one launch of tf_gemm_kernel behind its three entry points (host)
+template <int EPI>
+int launch_gemm(const char *what, const TfGemmArgs &P, bool nn, long R, int N, int nsplit, hipStream_t s) {
+  const long tiles = (R + FM - 1) / FM;
+  SPACAP_REQUIRE(tiles <= 2147483647L, "%s: too many rows", what);
+  const dim3 grid((unsigned)tiles, N / 128, nsplit);
+  if (nn) hipLaunchKernelGGL((tf_gemm_kernel<EPI, true>), grid, dim3(256), 0, s, P);
+  else hipLaunchKernelGGL((tf_gemm_kernel<EPI, false>), grid, dim3(256), 0, s, P);
+  SPACAP_CHECK_LAUNCH(what);
+  return SPACAP_OK;
 }
 
 }  // namespace
@@ -935,19 +907,6 @@ extern "C" int spacap_tf_rows_f32(const spacap_tf_rows_args *a, spacap_stream_t 
 }
 
 extern "C" int spacap_tf_rows_parts(long R) { return (int)((R + BM - 1) / BM); }
-
-namespace {
-template <int EPI>
-int launch_gemm(const char *what, const TfGemmArgs &P, bool nn, long R, int N, int nsplit, hipStream_t s) {
-  const long tiles = (R + FM - 1) / FM;
-  SPACAP_REQUIRE(tiles <= 2147483647L, "%s: too many rows", what);
-  const dim3 grid((unsigned)tiles, N / 128, nsplit);
-  if (nn) hipLaunchKernelGGL((tf_gemm_kernel<EPI, true>), grid, dim3(256), 0, s, P);
-  else hipLaunchKernelGGL((tf_gemm_kernel<EPI, false>), grid, dim3(256), 0, s, P);
-  SPACAP_CHECK_LAUNCH(what);
-  return SPACAP_OK;
-}
-}  // namespace
 
 extern "C" int spacap_tf_ffn1_f32(const float *x, const float *W, const float *bias, long R, int N, float drop_p, uint64_t seed,
                                   const uint64_t *seed_dev, float *h, spacap_stream_t stream) {
@@ -1033,134 +992,6 @@ extern "C" int spacap_tf_ffn_bf3_f32(int mode, const float *x, const void *piece
   hipStream_t s = spacap::as_stream(stream);
   if (mode == 0) hipLaunchKernelGGL((tf_ffn_bf3_kernel<false>), grid, dim3(256), 0, s, P);
   else hipLaunchKernelGGL((tf_ffn_bf3_kernel<true>), grid, dim3(256), 0, s, P);
-  SPACAP_CHECK_LAUNCH(what);
-  return SPACAP_OK;
-}
-
-extern "C" int spacap_decode_attn_f32(const float *qkv, float *kcache, float *vcache, long R, int h, int d_k, int T, int t, float scale,
-                                      float *out, spacap_stream_t stream) {
-  const char *what = "spacap_decode_attn_f32";
-  SPACAP_REQUIRE(R >= 0 && h == 8 && d_k == 16 && T >= 1 && T <= 32 && t >= 0 && t < T, "%s: (R=%ld, h=%d, d_k=%d, T=%d, t=%d) unsupported",
-                 what, R, h, d_k, T, t);
-  if (R == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(qkv && kcache && vcache && out && aligned16(qkv, kcache, vcache, out), "%s: null or unaligned pointer", what);
-  SPACAP_REQUIRE(R <= 2147483647L, "%s: too many sequences", what);
-  hipLaunchKernelGGL(decode_attn_kernel, dim3((unsigned)R), dim3(256), 0, spacap::as_stream(stream), qkv, kcache, vcache, T, t, scale, out);
-  SPACAP_CHECK_LAUNCH(what);
-  return SPACAP_OK;
-}
-
-// ---- greedy decoding: vocabulary projection + arg-max without the logits, and the next token's embedding ---------------------
-// (models/transformer_captioner.py:93-100 Generator: log_softmax(proj(x)) and :441-447: `_, next_word = torch.max(prob, dim=1)`;
-// the arg-max of the log-softmax is the arg-max of the logits.)  Round 4 ran F.linear on 2 048 x 3 001 logits + torch.argmax for
-// each of the 31 words.  Here a workgroup owns 16 sequences and one slice of the vocabulary: the slice's weight rows go through
-// LDS 64 at a time (next chunk's loads in flight), logits come out of v_mfma_f32_16x16x4_f32 (exact fp32 products) 16 words per
-// wave, and every lane keeps the running (best logit, first index) of its rows; the slices' winners [R][NS] are merged by
-// decode_next_kernel, which also writes the word into the caption and forms the next input row lut[word] sqrt(d) + pe[t].
-// Arithmetic: split-bf16 (three bf16 pieces per operand, the six piece products above 2^-24 on v_mfma_f32_16x16x32_bf16:
-// fp32-equivalent logits at 6/16 of the fp32-MFMA time -- 1.6 GFLOP per word on the fp32 pipe alone is 10 us).  The weight's
-// pieces Wp bf16 [3][V][128] are made once per decoding call (spacap_gemm_bf3_split_w_f32).
-// (the logit tile -- row split, weight staging, the six piece products -- and the compare are decode_common.hpp: shared with beam_search.hip)
-__global__ __launch_bounds__(256) void vocab_argmax_kernel(const float *__restrict__ x, const __bf16 *__restrict__ Wp, const float *__restrict__ bias,
-                                                           long R, int V, int per_slice, float *__restrict__ best_v, int *__restrict__ best_i) {
-  __shared__ __attribute__((aligned(16))) __bf16 s_w[VA_STAGE_ELEMS];
-  __shared__ float s_bv[4][VA_ROWS][17];
-  __shared__ int s_bi[4][VA_ROWS][17];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
-  const long row0 = (long)blockIdx.x * VA_ROWS;
-  const int ns = gridDim.y, sl = blockIdx.y;
-  const int v_beg = sl * per_slice, v_end = min(V, v_beg + per_slice);
-  SPACAP_VA_SPLIT_ROWS();   // bf16x8 a[kc][piece]: the sequences' rows as the A operand, split once
-  float bv[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  int bi[4] = {v_beg, v_beg, v_beg, v_beg};
-  SPACAP_VA_STAGING();      // stg, fetch(v0): the next chunk of the weight pieces in registers
-  fetch(v_beg < V ? v_beg : 0);
-  for (int v0 = v_beg; v0 < v_end; v0 += VA_CHUNK) {
-    __syncthreads();
-    SPACAP_VA_STORE_STAGE();
-    __syncthreads();
-    if (v0 + VA_CHUNK < v_end) fetch(v0 + VA_CHUNK);
-    const int v = v0 + 16 * w + l15;                    // this lane's word of the chunk
-    SPACAP_VA_TILE();                                   // acc, acc2: the 16 x 16 logits of this wave's words
-    if (v < v_end) {
-      const float bsv = bias[v];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {      // logit of sequence row0 + 4 lg + u, word v; words arrive in increasing order
-        const float val = (acc[u] + acc2[u]) + bsv;
-        if (val > bv[u]) bv[u] = val, bi[u] = v;
-      }
-    }
-  }
-  // merge across the 16 lanes and the 4 waves; ties go to the smaller word index (torch.max: first maximum)
-#pragma unroll
-  for (int u = 0; u < 4; ++u) s_bv[w][4 * lg + u][l15] = bv[u], s_bi[w][4 * lg + u][l15] = bi[u];
-  __syncthreads();
-  if (tid < 64) {
-    const int row = tid >> 2, ww = tid & 3;          // four threads per sequence, one wave's 16 candidates each
-    float m = -INFINITY;
-    int mi = 0x7fffffff;
-#pragma unroll
-    for (int l = 0; l < 16; ++l) {
-      const float val = s_bv[ww][row][l];
-      const int idx = s_bi[ww][row][l];
-      if (SPACAP_FIRST_MAX(val, idx, m, mi)) m = val, mi = idx;
-    }
-#pragma unroll
-    for (int o = 1; o <= 2; o <<= 1) {
-      const float om = __shfl_xor(m, o);
-      const int oi = __shfl_xor(mi, o);
-      if (SPACAP_FIRST_MAX(om, oi, m, mi)) m = om, mi = oi;
-    }
-    if (ww == 0 && row0 + row < R) {
-      best_v[(size_t)(row0 + row) * ns + sl] = m;
-      best_i[(size_t)(row0 + row) * ns + sl] = mi;
-    }
-  }
-}
-
-// word[r] = the best of the NS slice winners (first maximum); ys[r][t_out] = word; x[r, :] = lut[word] * scale + pe_row
-__global__ __launch_bounds__(256) void decode_next_kernel(const float *__restrict__ best_v, const int *__restrict__ best_i, int ns, long R,
-                                                          const float *__restrict__ lut, float scale, const float *__restrict__ pe_row,
-                                                          long long *__restrict__ ys, int ys_ld, int t_out, float *__restrict__ x) {
-  const long r = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
-  const int c4 = threadIdx.x & 31;
-  if (r >= R) return;
-  float m = -INFINITY;
-  int mi = 0x7fffffff;
-  for (int s = 0; s < ns; ++s) {
-    const float val = best_v[(size_t)r * ns + s];
-    const int idx = best_i[(size_t)r * ns + s];
-    if (SPACAP_FIRST_MAX(val, idx, m, mi)) m = val, mi = idx;
-  }
-  if (c4 == 0) ys[(size_t)r * ys_ld + t_out] = mi;
-  const f32x4 e = ld4(lut + (size_t)mi * D + 4 * c4), p = ld4(pe_row + 4 * c4);
-  st4(x + (size_t)r * D + 4 * c4, f32x4{e[0] * scale + p[0], e[1] * scale + p[1], e[2] * scale + p[2], e[3] * scale + p[3]});
-}
-
-/* One greedy-decoding step's word choice (models/transformer_captioner.py:441-447 with the Generator of :93-100): x f32 [R,128] the
-   decoder's output rows, Wp bf16 [3][V][128] = the pieces of the projection weight (spacap_gemm_bf3_split_w_f32), bias f32 [V]
-   -> ys i64 [R][ys_ld] column t_out = arg-max word (first maximum), and the next
-   step's input rows x_next f32 [R,128] = lut[word] * scale + pe_row (lut f32 [V,128], pe_row f32 [128]).
-   workspace: spacap_decode_word_workspace_bytes(R, V) bytes (the vocabulary slices' winners). */
-extern "C" size_t spacap_decode_word_workspace_bytes(long R, int V) { return R > 0 && V > 0 ? (size_t)R * va_slices(R, V) * 8 : 0; }
-extern "C" int spacap_decode_word_f32(const float *x, const void *W, const float *bias, long R, int V, const float *lut, float scale,
-                                      const float *pe_row, int64_t *ys, int ys_ld, int t_out, float *x_next, void *workspace,
-                                      spacap_stream_t stream) {
-  const char *what = "spacap_decode_word_f32";
-  SPACAP_REQUIRE(R >= 0 && V >= 1 && ys_ld >= 1 && t_out >= 0 && t_out < ys_ld, "%s: bad sizes", what);
-  if (R == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(x && W && bias && lut && pe_row && ys && x_next && workspace && aligned16(x, W, lut, pe_row, x_next),
-                 "%s: null or unaligned pointer", what);
-  SPACAP_REQUIRE(R <= 16L * 2147483647L, "%s: too many sequences", what);
-  const int ns = va_slices(R, V);
-  const int per = va_per_slice(V, ns);   // whole chunks per slice
-  float *bv = static_cast<float *>(workspace);
-  int *bi = reinterpret_cast<int *>(bv + (size_t)R * ns);
-  hipStream_t s = spacap::as_stream(stream);
-  hipLaunchKernelGGL(vocab_argmax_kernel, dim3((unsigned)((R + VA_ROWS - 1) / VA_ROWS), ns), dim3(256), 0, s, x, static_cast<const __bf16 *>(W),
-                     bias, R, V, per, bv, bi);
-  hipLaunchKernelGGL(decode_next_kernel, dim3((unsigned)((R + 7) / 8)), dim3(256), 0, s, bv, bi, ns, R, lut, scale, pe_row,
-                     reinterpret_cast<long long *>(ys), ys_ld, t_out, x_next);
   SPACAP_CHECK_LAUNCH(what);
   return SPACAP_OK;
 }

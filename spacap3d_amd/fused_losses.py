@@ -178,7 +178,7 @@ def caption_head_loss(logits, lang_ids, good):
 class ProposalDecode(Function):
     """(net (B,CH,K), agg_xyz (B,K,3), mean_size (NS,3)) -> (nt (B,K,CH), center, heading_residuals, size_residuals, bbox_corner
     f64 (B,K,8,3), bbox_mask, sem_cls, size_cls): decode_scores + decode_pred_box (models/proposal_module.py:81-158) as one
-    launch each way (csrc/decode.hip)."""
+    launch each way (csrc/proposal_decode.hip)."""
 
     @staticmethod
     def forward(ctx, net, agg_xyz, mean_size, mean_size_f64, NH, NS):
@@ -306,7 +306,7 @@ def l2norm_rows(x):
 
 class VoteAssemble(Function):
     """vote_xyz, vote_features (point-major) from the voting module's last convolution, one launch each way
-    (csrc/decode.hip: vote_assemble_*; models/voting_module.py:49-60 with vote_factor 1)."""
+    (csrc/proposal_decode.hip: vote_assemble_*; models/voting_module.py:49-60 with vote_factor 1)."""
 
     @staticmethod
     def forward(ctx, net, seed_xyz, seed_features):

@@ -138,7 +138,7 @@ class LnQkv(Function):
 
 # ---- split-bf16 feed-forward block for tall inputs (csrc/tf_layer.hip: tf_ffn_bf3_kernel) ---------------------------------------
 # The kernel takes the layer's weights as pre-split bf16 piece images.  ``refresh_ffn_pieces(layers)`` (re)builds the images of a
-# whole stack with ONE launch -- run_stack / greedy_decode call it at the start of every forward, i.e. after any optimizer update
+# whole stack with ONE launch -- run_stack and the caption decoders (caption_decode.py) call it at the start of every forward, i.e. after any optimizer update
 # and before the backward of the same step -- and registers them under the address of w_1's weight; ``_ffn`` uses them when the
 # input has more than FFN_BF3_MIN_ROWS rows and falls back to the fp32-MFMA kernel otherwise (few rows: latency bound either way).
 FFN_BF3 = True
@@ -420,16 +420,6 @@ def stack_supported(layers, x):
     return True
 
 
-def decode_supported(layers, x, n_words):
-    """True when ``greedy_decode`` can run: everything ``stack_supported`` asks for, plus what ``spacap_decode_attn_f32``
-    requires (h = 8, d_k = 16, at most 32 cached positions) and one feed-forward width for the whole stack (one partial-sum
-    buffer).  Anything else decodes through the cached per-operator path (``decode_incremental``)."""
-    if not stack_supported(layers, x) or n_words + 1 > 32:
-        return False
-    dff = layers[0].feed_forward.w_1.out_features
-    return all(l.self_attn.h == 8 and l.self_attn.d_k == 16 and l.feed_forward.w_1.out_features == dff for l in layers)
-
-
 def run_stack(layers, final_norm, x, mask):
     """The N pre-norm layers (self-attention + feed-forward each) followed by ``final_norm``
     (models/transformer_captioner.py: Encoder :166-178 / Decoder :193-207 in early-guide mode)."""
@@ -479,201 +469,3 @@ def run_stack(layers, final_norm, x, mask):
             (out,) = Ffn2Ln.apply(h, parts, x1, ff.w_1.weight, ff.w_2.weight, ff.w_2.bias, final_norm.a_2, final_norm.b_2,
                                   final_norm.eps, p3, pf, seed(p3), None, None)
     return out
-
-
-@torch.no_grad()
-def greedy_decode(dec, generator, embed, pe, indicator, sos, n_words):
-    """Greedy decoding of R sequences through the early-guide decoder stack ``dec`` with pre-allocated key / value caches
-    (models/transformer_captioner.py:402-453; the reference re-runs encoder and decoder prefix for every word).  Position 0
-    is the object indicator token (R, 128), position 1 the start symbol, then every chosen word is fed back; one token per
-    sequence per step, four launches per layer and step (the training kernels with dropout off + spacap_decode_attn_f32).
-    The word choice of a step -- vocabulary projection + arg-max + the chosen word's embedding row -- is one library call
-    (csrc/tf_layer.hip: vocab_argmax_kernel / decode_next_kernel: no logits in HBM, no BLAS call).
-    Returns the (R, n_words) int64 word ids."""
-    import math
-    layers = list(dec.layers)
-    R, dev = indicator.shape[0], indicator.device
-    T = n_words + 1
-    st = torch.cuda.current_stream(dev).cuda_stream
-    packs = [_packed(l.self_attn)[:2] for l in layers]
-    h, dk = layers[0].self_attn.h, layers[0].self_attn.d_k
-    dff = layers[0].feed_forward.w_1.out_features
-    S = dff // 128
-    scale = 1.0 / math.sqrt(dk)
-    pieces = None
-    if FFN_BF3 and R > FFN_BF3_MIN_ROWS:
-        refresh_ffn_pieces(layers)
-        pieces = [_FFN_PIECES.get(l.feed_forward.w_1.weight.data_ptr()) for l in layers]
-        pieces = [e[1] for e in pieces] if all(e is not None for e in pieces) else None
-    with torch.cuda.device(dev):
-        kc = [_new(dev, R, T, D_MODEL) for _ in layers]
-        vc = [_new(dev, R, T, D_MODEL) for _ in layers]
-        qkv, a, x1, x2, n2, n = _new(dev, R, 3 * D_MODEL), _new(dev, R, D_MODEL), _new(dev, R, D_MODEL), _new(dev, R, D_MODEL), \
-            _new(dev, R, D_MODEL), _new(dev, R, D_MODEL)
-        parts = _new(dev, S, R, D_MODEL)
-        ys = torch.empty(R, n_words, dtype=torch.long, device=dev)
-        sqrt_d = math.sqrt(embed.d_model)
-        x = indicator.contiguous()
-        lut, gw, gb = embed.lut.weight.contiguous(), generator.proj.weight.contiguous(), generator.proj.bias.contiguous()
-        V = gw.shape[0]
-        from .linear import bf3_pieces
-        gwp = bf3_pieces(gw)                            # the projection weight's three bf16 pieces, once per call
-        pe_rows = pe[0, :T].contiguous()
-        xw = _new(dev, R, D_MODEL)                      # the next step's input rows (written by the word kernel)
-        ws = torch.empty(int(lib.spacap_decode_word_workspace_bytes(R, V)), dtype=torch.uint8, device=dev)
-        for t in range(T):
-            if t == 1:
-                x = (lut[int(sos)] * sqrt_d + pe_rows[0]).expand(R, D_MODEL).contiguous()   # every sequence starts with <sos>
-            elif t > 1:
-                x = xw
-            n0 = layers[0].sublayer[0].norm
-            _rows(0, R, dev, res=x, ln_a=n0.a_2, ln_b=n0.b_2, eps=n0.eps, w2=packs[0][0], bias2=packs[0][1], n2=3 * D_MODEL, out2=qkv)
-            xres = x
-            for i, l in enumerate(layers):
-                sa, ff, nf = l.self_attn, l.feed_forward, l.sublayer[-1].norm
-                check(lib.spacap_decode_attn_f32(qkv.data_ptr(), kc[i].data_ptr(), vc[i].data_ptr(), R, h, dk, T, t, scale, a.data_ptr(),
-                                                 st), "spacap_decode_attn_f32")
-                _rows(0, R, dev, a1=a, w1=sa.linears[-1].weight, bias1=sa.linears[-1].bias, k1=D_MODEL, res=xres, x_out=x1,
-                      ln_a=nf.a_2, ln_b=nf.b_2, eps=nf.eps, n_out=n2)
-                if pieces is not None:
-                    check(lib.spacap_tf_ffn_bf3_f32(0, n2.data_ptr(), pieces[i].data_ptr(), ff.w_1.bias.data_ptr(), None, R, dff, 0.0, 0,
-                                                    None, None, parts.data_ptr(), st), "spacap_tf_ffn_bf3_f32")
-                else:
-                    check(lib.spacap_tf_ffn_f32(0, n2.data_ptr(), ff.w_1.weight.data_ptr(), ff.w_2.weight.data_ptr(),
-                                                ff.w_1.bias.data_ptr(), None, R, dff, 0.0, 0, None, None, parts.data_ptr(), st),
-                          "spacap_tf_ffn_f32")
-                if i + 1 < len(layers):
-                    nn_ = layers[i + 1].sublayer[0].norm
-                    _rows(0, R, dev, a1=parts, nparts=S, bias1=ff.w_2.bias, res=x1, x_out=x2, ln_a=nn_.a_2, ln_b=nn_.b_2, eps=nn_.eps,
-                          w2=packs[i + 1][0], bias2=packs[i + 1][1], n2=3 * D_MODEL, out2=qkv)
-                    xres = x2
-                else:
-                    _rows(0, R, dev, a1=parts, nparts=S, bias1=ff.w_2.bias, res=x1, ln_a=dec.norm.a_2, ln_b=dec.norm.b_2,
-                          eps=dec.norm.eps, n_out=n)
-            if t >= 1:
-                # ys[:, t - 1] = argmax_v (n W^T + b); xw = lut[word] sqrt(d) + pe[t]: the input of step t + 1
-                check(lib.spacap_decode_word_f32(n.data_ptr(), gwp.data_ptr(), gb.data_ptr(), R, V, lut.data_ptr(), sqrt_d,
-                                                 pe_rows[min(t, T - 1)].data_ptr(), ys.data_ptr(), n_words, t - 1, xw.data_ptr(),
-                                                 ws.data_ptr(), st), "spacap_decode_word_f32")
-    return ys
-
-
-@torch.no_grad()
-def beam_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, beam_size, length_penalty=0.0, return_all=False, trace=None):
-    """Beam-search decoding of R sequences with ``beam_size`` = W hypotheses each (1 <= W <= 8): the ``greedy_decode`` loop at
-    R W rows (row r W + w = hypothesis w of sequence r) through the same row / feed-forward kernels -- they are
-    row-independent -- with three kernels of csrc/beam_search.hip in place of the greedy ones: attention that reads a
-    hypothesis' history through an ancestor table (the key / value caches are never reordered), the W best log-probabilities
-    of every row without the logits in HBM, and one selection per sequence; the trace is backtracked once at the end.  The
-    semantics are DESIGN.md section 7e (the reference has no beam search); no step reads a value back on the host, so the
-    call can be captured in a graph like the greedy loop.  Cache memory: 12 R W T 512 bytes for 6 layers.
-    Returns ``(ys (R, n_words) int64, score (R,) float32)`` -- the winner's words (eos repeats after the first eos) and its
-    sum of log-probabilities -- and with ``return_all`` also ``(beams (R, W, n_words) int64, scores (R, W), lengths (R, W))``.  ``trace``: a dict that
-    receives the selections, ``parent`` int8 and ``word`` int32, each (n_words, R, W)."""
-    import math
-    layers = list(dec.layers)
-    R, dev = indicator.shape[0], indicator.device
-    W = int(beam_size)
-    T = n_words + 1
-    lut, gw, gb = embed.lut.weight.contiguous(), generator.proj.weight.contiguous(), generator.proj.bias.contiguous()
-    V = gw.shape[0]
-    if not 1 <= W <= 8 or W > V:
-        raise ValueError(f"beam_decode: beam_size {W} unsupported (1 <= beam_size <= 8 and beam_size <= vocabulary size {V})")
-    RW = R * W
-    st = torch.cuda.current_stream(dev).cuda_stream
-    packs = [_packed(l.self_attn)[:2] for l in layers]
-    h, dk = layers[0].self_attn.h, layers[0].self_attn.d_k
-    dff = layers[0].feed_forward.w_1.out_features
-    S = dff // 128
-    scale = 1.0 / math.sqrt(dk)
-    pieces = None
-    if FFN_BF3 and RW > FFN_BF3_MIN_ROWS:
-        refresh_ffn_pieces(layers)
-        pieces = [_FFN_PIECES.get(l.feed_forward.w_1.weight.data_ptr()) for l in layers]
-        pieces = [e[1] for e in pieces] if all(e is not None for e in pieces) else None
-    with torch.cuda.device(dev):
-        try:
-            kc = [_new(dev, RW, T, D_MODEL) for _ in layers]
-            vc = [_new(dev, RW, T, D_MODEL) for _ in layers]
-        except torch.cuda.OutOfMemoryError as e:
-            need = 2 * len(layers) * RW * T * D_MODEL * 4
-            raise RuntimeError(f"beam_decode: the key / value caches of {R} sequences x {W} hypotheses need {need / 2**30:.2f} GiB "
-                               f"({len(layers)} layers x 2 x {RW} rows x {T} positions x 512 B) and could not be allocated: "
-                               "decode fewer scenes per call or lower beam_size") from e
-        qkv, a, x1, x2, n2, n = _new(dev, RW, 3 * D_MODEL), _new(dev, RW, D_MODEL), _new(dev, RW, D_MODEL), _new(dev, RW, D_MODEL), \
-            _new(dev, RW, D_MODEL), _new(dev, RW, D_MODEL)
-        parts = _new(dev, S, RW, D_MODEL)
-        sqrt_d = math.sqrt(embed.d_model)
-        x = indicator.contiguous().repeat_interleave(W, 0)    # positions 0 and 1: the W rows of a sequence are identical
-        from .linear import bf3_pieces
-        gwp = bf3_pieces(gw)                            # the projection weight's three bf16 pieces, once per call
-        pe_rows = pe[0, :T].contiguous()
-        xw = _new(dev, RW, D_MODEL)                     # the next step's input rows (written by the selection kernel)
-        ws = torch.empty(int(lib.spacap_beam_topw_workspace_bytes(RW, V, W)), dtype=torch.uint8, device=dev)
-        top_lp = torch.empty(RW, W, dtype=torch.float32, device=dev)
-        top_wd = torch.empty(RW, W, dtype=torch.int32, device=dev)
-        # hypothesis state, double-buffered: before the first selection hypothesis 0 has score 0, the others are dead
-        score = [torch.full((R, W), float("-inf"), dtype=torch.float32, device=dev) for _ in range(2)]
-        score[1][:, 0] = 0.0                           # (the selection after position t reads buffer t % 2)
-        fin = [torch.zeros(R, W, dtype=torch.int32, device=dev) for _ in range(2)]
-        ln = [torch.zeros(R, W, dtype=torch.int32, device=dev) for _ in range(2)]
-        anc = [torch.arange(W, dtype=torch.int8, device=dev).view(1, W, 1).expand(R, W, T).contiguous() for _ in range(2)]
-        tr_parent = torch.empty(n_words, R, W, dtype=torch.int8, device=dev)
-        tr_word = torch.empty(n_words, R, W, dtype=torch.int32, device=dev)
-        for t in range(T):
-            if t == 1:
-                x = (lut[int(sos)] * sqrt_d + pe_rows[0]).expand(RW, D_MODEL).contiguous()   # every hypothesis starts with <sos>
-            elif t > 1:
-                x = xw
-            n0 = layers[0].sublayer[0].norm
-            _rows(0, RW, dev, res=x, ln_a=n0.a_2, ln_b=n0.b_2, eps=n0.eps, w2=packs[0][0], bias2=packs[0][1], n2=3 * D_MODEL, out2=qkv)
-            xres = x
-            for i, l in enumerate(layers):
-                sa, ff, nf = l.self_attn, l.feed_forward, l.sublayer[-1].norm
-                check(lib.spacap_decode_attn_beam_f32(qkv.data_ptr(), kc[i].data_ptr(), vc[i].data_ptr(), anc[t % 2].data_ptr(), R, W, h, dk,
-                                                      T, t, scale, a.data_ptr(), st), "spacap_decode_attn_beam_f32")
-                _rows(0, RW, dev, a1=a, w1=sa.linears[-1].weight, bias1=sa.linears[-1].bias, k1=D_MODEL, res=xres, x_out=x1,
-                      ln_a=nf.a_2, ln_b=nf.b_2, eps=nf.eps, n_out=n2)
-                if pieces is not None:
-                    check(lib.spacap_tf_ffn_bf3_f32(0, n2.data_ptr(), pieces[i].data_ptr(), ff.w_1.bias.data_ptr(), None, RW, dff, 0.0, 0,
-                                                    None, None, parts.data_ptr(), st), "spacap_tf_ffn_bf3_f32")
-                else:
-                    check(lib.spacap_tf_ffn_f32(0, n2.data_ptr(), ff.w_1.weight.data_ptr(), ff.w_2.weight.data_ptr(),
-                                                ff.w_1.bias.data_ptr(), None, RW, dff, 0.0, 0, None, None, parts.data_ptr(), st),
-                          "spacap_tf_ffn_f32")
-                if i + 1 < len(layers):
-                    nn_ = layers[i + 1].sublayer[0].norm
-                    _rows(0, RW, dev, a1=parts, nparts=S, bias1=ff.w_2.bias, res=x1, x_out=x2, ln_a=nn_.a_2, ln_b=nn_.b_2, eps=nn_.eps,
-                          w2=packs[i + 1][0], bias2=packs[i + 1][1], n2=3 * D_MODEL, out2=qkv)
-                    xres = x2
-                else:
-                    _rows(0, RW, dev, a1=parts, nparts=S, bias1=ff.w_2.bias, res=x1, ln_a=dec.norm.a_2, ln_b=dec.norm.b_2,
-                          eps=dec.norm.eps, n_out=n)
-            if t >= 1:
-                # the W best (log-probability, word) of every row, then one selection per sequence: state t % 2 -> (t + 1) % 2,
-                # trace[t - 1], the ancestor table for position t + 1 and xw = lut[word] sqrt(d) + pe[t], the input of step t + 1
-                check(lib.spacap_beam_topw_f32(n.data_ptr(), gwp.data_ptr(), gb.data_ptr(), RW, V, W, top_lp.data_ptr(), top_wd.data_ptr(),
-                                               ws.data_ptr(), st), "spacap_beam_topw_f32")
-                i0, i1 = t % 2, (t + 1) % 2
-                check(lib.spacap_beam_step_f32(top_lp.data_ptr(), top_wd.data_ptr(), R, W, V, T, t, int(eos), score[i0].data_ptr(),
-                                               fin[i0].data_ptr(), ln[i0].data_ptr(), score[i1].data_ptr(), fin[i1].data_ptr(),
-                                               ln[i1].data_ptr(), anc[i0].data_ptr(), anc[i1].data_ptr(), tr_parent.data_ptr(),
-                                               tr_word.data_ptr(), lut.data_ptr(), sqrt_d, pe_rows[min(t, T - 1)].data_ptr(), xw.data_ptr(),
-                                               st), "spacap_beam_step_f32")
-        last = T % 2                                    # the buffer the last selection (t = T - 1) wrote
-        ys = torch.empty(R, n_words, dtype=torch.long, device=dev)
-        best = torch.empty(R, dtype=torch.float32, device=dev)
-        beams = scores = lengths = None
-        if return_all:
-            beams = torch.empty(R, W, n_words, dtype=torch.long, device=dev)
-            scores = torch.empty(R, W, dtype=torch.float32, device=dev)
-            lengths = torch.empty(R, W, dtype=torch.int32, device=dev)
-        check(lib.spacap_beam_finish_f32(score[last].data_ptr(), ln[last].data_ptr(), tr_parent.data_ptr(), tr_word.data_ptr(), R, W, n_words,
-                                         float(length_penalty), ys.data_ptr(), best.data_ptr(),
-                                         beams.data_ptr() if return_all else None, scores.data_ptr() if return_all else None,
-                                         lengths.data_ptr() if return_all else None, st), "spacap_beam_finish_f32")
-    if trace is not None:
-        trace["parent"], trace["word"] = tr_parent, tr_word
-    if return_all:
-        return ys, best, beams, scores, lengths
-    return ys, best

@@ -644,22 +644,22 @@ class TransformerDecoderModel(nn.Module):
         else:
             indicator, dec_memory = obj_flat.unsqueeze(1), memory
         embed, pos = self.model.tgt_embed[0], self.model.tgt_embed[1]
-        st = getattr(ops(), "tf_stack", None)
-        fused = self.early_guide and not self.training and st is not None \
-            and st.decode_supported(dec.layers, indicator.squeeze(1), MAX_DES_LEN + 1)
+        cd = getattr(ops(), "caption_decode", None)
+        fused = self.early_guide and not self.training and cd is not None \
+            and cd.decode_supported(dec.layers, indicator.squeeze(1), MAX_DES_LEN + 1)
         if beam and fused and not self.beam_generic:
             # the greedy loop below at B K W rows: top-W log-probabilities, one selection per sequence, attention through an
-            # ancestor table (tf_layer.beam_decode, csrc/beam_search.hip)
+            # ancestor table (caption_decode.beam_decode, csrc/caption_decode.hip)
             self.last_beam_trace = {}       # parent int8 / word int32 (n_words, R, W): the selections, for parity tests
-            got = st.beam_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), self.word_to_idx["sos"],
+            got = cd.beam_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), self.word_to_idx["sos"],
                                  self.word_to_idx["eos"], MAX_DES_LEN + 1, W, alpha, return_all=self.beam_return_all,
                                  trace=self.last_beam_trace)
             return self._beam_outputs(ep, B, K, *got)
         if beam:
             return self._beam_generic(ep, B, K, W, alpha, dec, indicator, embed, pos)
         if fused:
-            # pre-allocated key / value caches, one token per sequence and step, four launches per layer (tf_layer.greedy_decode)
-            words = st.greedy_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), self.word_to_idx["sos"],
+            # pre-allocated key / value caches, one token per sequence and step, four launches per layer (caption_decode.greedy_decode)
+            words = cd.greedy_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), self.word_to_idx["sos"],
                                      MAX_DES_LEN + 1)
             ep["lang_cap"] = words.view(B, K, -1)
             return ep

@@ -1,6 +1,6 @@
 """The beam-search contract, restated in plain numpy float64 with no shortcut: every candidate of every
 hypothesis is enumerated and sorted.  Not a test module; tests/test_beam_search*.py compare the kernels of
-csrc/beam_search.hip and spacap3d_amd/beam_search.py against it.
+csrc/caption_decode.hip and spacap3d_amd/beam_search.py against it.
 
 Each sequence keeps W hypotheses (score, last word, finished, length); at the start hypothesis 0 has score 0 and the others
 -inf (dead).  One selection: a live unfinished hypothesis j offers (score_j + logp_j[v], j, v) for EVERY word v, a finished one

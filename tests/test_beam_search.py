@@ -1,6 +1,6 @@
 """Beam search without a GPU: spacap3d_amd.beam_search (the generic path) against the float64 restatement of the contract
 (tests/beam_search_restated.py), the width-1 beam against the reference's recorded greedy captions, and
-the C ABI of csrc/beam_search.hip."""
+the C ABI of csrc/caption_decode.hip."""
 import os
 import re
 import sys

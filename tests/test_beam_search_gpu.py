@@ -1,6 +1,7 @@
-"""Beam-search decoding on the MI355X (csrc/beam_search.hip, tf_layer.beam_decode, transformer_captioner.forward_eval) against
-the float64 restatement of the contract (tests/beam_search_restated.py), the greedy decoder (a beam of
-width 1) and the generic path (spacap3d_amd/beam_search.py)."""
+"""Beam-search decoding on the MI355X (csrc/caption_decode.hip, caption_decode.beam_decode, transformer_captioner.forward_eval)
+against the float64 restatement of the contract (tests/beam_search_restated.py), the greedy decoder (a beam
+of width 1) and the generic path (spacap3d_amd/beam_search.py).  The greedy decoder's own kernels and the step the two decoders
+share: tests/test_caption_decode_gpu.py."""
 import math
 
 import numpy as np
@@ -219,9 +220,10 @@ def test_selection_and_backtracking_equal_the_restatement(R, W):
 
 
 # ---- 6. attention through the ancestor table -------------------------------------------------------------------------------------
-def test_attention_reads_a_hypothesis_history_through_the_ancestor_table():
+@pytest.mark.parametrize("R,W,T", [(1, 1, 1), (2, 8, 5), (5, 3, 32)])   # one key and nothing cached; the widest table and a row stride that is not 32
+def test_attention_reads_a_hypothesis_history_through_the_ancestor_table(R, W, T):
     lib, check, st = _lib()
-    R, W, T, h, dk = 5, 3, 32, 8, 16
+    h, dk = 8, 16
     RW = R * W
     g = torch.Generator().manual_seed(3)
     ident = torch.arange(W, dtype=torch.int8, device=DEV).view(1, W, 1).expand(R, W, T).contiguous()
@@ -283,24 +285,24 @@ def _through_first_eos(tokens, eos):
 
 def test_width_one_is_the_greedy_decoder(scene, monkeypatch):
     """beam_decode(W = 1) against greedy_decode on the same inputs, word for word through each row's first eos (behind it a
-    beam repeats eos; the greedy loop goes on).  Exact: the logit arithmetic is ONE definition (csrc/decode_common.hpp), the
+    beam repeats eos; the greedy loop goes on).  Exact: the logit arithmetic is ONE definition (csrc/caption_decode.hip), the
     first-maximum order does not depend on how the vocabulary is sliced, and the other kernels are row-independent."""
-    from spacap3d_amd import tf_layer
+    from spacap3d_amd import caption_decode
     model, data, d = scene
     seen = {}
-    real = tf_layer.greedy_decode
+    real = caption_decode.greedy_decode
 
     def spy(*a):
         seen["args"] = a
         return real(*a)
 
-    monkeypatch.setattr(tf_layer, "greedy_decode", spy)
+    monkeypatch.setattr(caption_decode, "greedy_decode", spy)
     with torch.no_grad():
         g = model.caption.forward_eval(dict(d))["lang_cap"]
     dec, gen, embed, pe, indicator, sos, n_words = seen["args"]
     eos = model.caption.word_to_idx["eos"]
     tr = {}
-    ys, score = tf_layer.beam_decode(dec, gen, embed, pe, indicator, sos, eos, n_words, 1, trace=tr)
+    ys, score = caption_decode.beam_decode(dec, gen, embed, pe, indicator, sos, eos, n_words, 1, trace=tr)
     g = g.reshape(-1, n_words)
     assert torch.equal(g, d["lang_cap"].reshape(-1, n_words)) and ys.shape == g.shape
     keep = _through_first_eos(g, eos)
@@ -309,6 +311,7 @@ def test_width_one_is_the_greedy_decoder(scene, monkeypatch):
     assert bool((ys[~keep] == eos).all())
     assert bool((tr["parent"] == 0).all()) and torch.equal(tr["word"][:, :, 0].t().long(), ys)
     assert bool(torch.isfinite(score).all()) and bool((score <= 0).all())
+
 
 
 SCORE_TOL = 4 * 1.81e-5    # (a): four times the largest deviation measured on the MI355X (1.81e-5, see the test); must stay below 1e-3
@@ -337,7 +340,7 @@ def _teacher_forced_score(model, d, tokens, eos):
 
 
 def _fused_generic_cpu(model, d, W):
-    """forward_eval three ways on the detector outputs ``d``: fused (tf_layer.beam_decode), generic on the GPU, generic on the
+    """forward_eval three ways on the detector outputs ``d``: fused (caption_decode.beam_decode), generic on the GPU, generic on the
     CPU oracle backend.  Returns the two GPU outputs, the three traces and the teacher-forced scores of the fused winners."""
     import copy
     from oracle.attention_ref import OracleBackend
@@ -349,7 +352,7 @@ def _fused_generic_cpu(model, d, W):
             cap.last_beam_trace = None
             fused = cap.forward_eval(dict(d), beam_size=W)
             tz = {k: v.cpu() for k, v in cap.last_beam_trace.items()}
-            assert "gap" not in tz, "forward_eval did not take tf_layer.beam_decode"
+            assert "gap" not in tz, "forward_eval did not take caption_decode.beam_decode"
             cap.beam_generic = True
             gen = cap.forward_eval(dict(d), beam_size=W)
             tg = {k: v.cpu() for k, v in cap.last_beam_trace.items()}
@@ -371,7 +374,7 @@ def _differing(a, b):
 
 
 def test_fused_beam_search_against_the_generic_path(scene):
-    """W = 3, forward_eval on the fused path (tf_layer.beam_decode) against the generic one (beam_search.beam_search over
+    """W = 3, forward_eval on the fused path (caption_decode.beam_decode) against the generic one (beam_search.beam_search over
     decode_incremental).
     (a) lang_cap_score equals the winner's words teacher-forced through the uncached decoder, summed through the first eos,
         within SCORE_TOL = 4 x the largest deviation measured on the MI355X (1.81e-5 on scores down to -80: fp32 accumulation

@@ -129,7 +129,7 @@ def test_proposal_decode_matches_the_composition(B, K, NH):
 
 @pytest.mark.parametrize("B,C,N", [(8, 256, 1024), (2, 100, 77), (1, 256, 33)])
 def test_vote_assemble_matches_the_tensor_operations(B, C, N):
-    """fused_losses.vote_assemble (csrc/decode.hip) against the voting module's own lines (models/voting_module.py:49-60):
+    """fused_losses.vote_assemble (csrc/proposal_decode.hip) against the voting module's own lines (models/voting_module.py:49-60):
     vote_xyz and the point-major vote features bit for bit, and the gradients of the convolution output and of the seed
     features (exact: every element has one contribution)."""
     from spacap3d_amd.fused_losses import vote_assemble

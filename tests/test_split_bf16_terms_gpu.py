@@ -344,7 +344,7 @@ def test_feed_forward_block(q):
     _settle(site_tf_ffn(q))
 
 
-# ---- csrc/decode_common.hpp: the logit tile of both caption decoders ------------------------------------------------------------------------
+# ---- csrc/caption_decode.hip: the logit tile of both caption decoders ------------------------------------------------------------------------
 @pytest.mark.parametrize("q", TERMS)
 def test_decoder_logits(q):
     from spacap3d_amd.linear import bf3_pieces

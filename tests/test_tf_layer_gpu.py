@@ -247,29 +247,6 @@ def test_dropout_masks_agree_between_forward_and_backward(tf, kind):
         assert rel(h0, torch.relu(n2.double() @ W1.double().t() + b1.double())) < 2e-6
 
 
-def test_decode_attention_step_over_the_cache(tf):
-    """spacap_decode_attn_f32: appending the new token's k, v and attending over positions 0..t equals the last row of causal
-    attention over the whole prefix (what the reference recomputes at every word, models/transformer_captioner.py:435-438)."""
-    from spacap3d_amd._native import check, lib
-    R, T, h, dk = 37, 32, 8, 16
-    kc, vc = torch.zeros(R, T, 128, device=DEV), torch.zeros(R, T, 128, device=DEV)
-    out = torch.empty(R, 128, device=DEV)
-    st = torch.cuda.current_stream().cuda_stream
-    rows = []
-    for t in range(T):
-        qkv = _rand(R, 384, seed=100 + t)
-        rows.append(qkv)
-        check(lib.spacap_decode_attn_f32(qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(), R, h, dk, T, t, 0.25, out.data_ptr(), st), "dec")
-        allr = torch.stack(rows, 1).double()                                   # (R, t+1, 384)
-        q = allr[:, -1, :128].view(R, h, 1, dk)
-        k = allr[:, :, 128:256].view(R, t + 1, h, dk).transpose(1, 2)
-        v = allr[:, :, 256:].view(R, t + 1, h, dk).transpose(1, 2)
-        p = torch.softmax(q @ k.transpose(-1, -2) * 0.25, -1)
-        want = (p @ v).transpose(1, 2).reshape(R, 128)
-        assert rel(out, want) < 3e-6, t
-        assert torch.equal(kc[:, t], qkv[:, 128:256]) and torch.equal(vc[:, t], qkv[:, 256:])
-
-
 @pytest.mark.parametrize("B,L,mask_kind,p", [(2, 256, "key", 0.0), (3, 32, "causal", 0.0), (2, 256, "key", 0.2), (1, 96, None, 0.0)])
 def test_single_launch_attention_backward_equals_the_two_launch_form(tf, B, L, mask_kind, p):
     """spacap_mha_bwd_delta_f32 (delta = sum_d out d_out handed in, dQ and dK/dV halves in one launch) against
@@ -325,47 +302,14 @@ def test_eval_with_other_head_counts_decodes_through_the_cached_operator_path(tf
     model = build_default(vocab_size=120, num_proposal=32, N=2, h=h, d_ff=256).to(DEV).eval()
     dec = model.caption.model.decoder
     x = torch.zeros(4, 128, device=DEV)
-    assert tf.stack_supported(dec.layers, x) and not tf.decode_supported(dec.layers, x, 31)
+    from spacap3d_amd import caption_decode
+    assert tf.stack_supported(dec.layers, x) and not caption_decode.decode_supported(dec.layers, x, 31)
     data = synthetic_batch(2, 4096, DEV, seed=1, vocab=120)
     with torch.no_grad():
         d = model(dict(data), is_eval=True)
         d2 = model.caption.forward_eval(dict(d), use_cache=False)
     assert d["lang_cap"].shape == d2["lang_cap"].shape == (2, 32, 31)
     assert (d["lang_cap"] == d2["lang_cap"]).float().mean() > 0.995
-
-
-@pytest.mark.parametrize("R,V", [(2048, 3001), (37, 40), (16, 64), (300, 1000)])
-def test_decode_word_choice_without_logits(R, V):
-    """spacap_decode_word_f32 (csrc/tf_layer.hip: vocab_argmax_kernel + decode_next_kernel): the greedy word of every sequence
-    = arg-max of x W^T + b (models/transformer_captioner.py:441-447 on the Generator of :93-100; first maximum on ties, as
-    torch.max), written into the caption, and the next input row lut[word] sqrt(d) + pe.  Against float64 logits: the chosen
-    word's logit is within fp32 rounding of the maximum (an exact tie in float64 picks the smaller index)."""
-    import math
-    from spacap3d_amd._native import check, lib
-    g = torch.Generator().manual_seed(R + V)
-    x = torch.randn(R, 128, generator=g).to(DEV)
-    W, b = (0.3 * torch.randn(V, 128, generator=g)).to(DEV), torch.randn(V, generator=g).to(DEV)
-    W[7] = W[3]
-    b[7] = b[3]                                      # two identical words: the first one must win wherever they lead
-    x[0] = 0.0
-    b[3] = b[7] = 50.0                               # ... which they do for row 0 (all-zero input: logits = bias)
-    lut, pe = torch.randn(V, 128, generator=g).to(DEV), torch.randn(128, generator=g).to(DEV)
-    ys = torch.full((R, 5), -1, dtype=torch.long, device=DEV)
-    xn = torch.empty(R, 128, device=DEV)
-    ws = torch.empty(int(lib.spacap_decode_word_workspace_bytes(R, V)), dtype=torch.uint8, device=DEV)
-    scale = math.sqrt(128.0)
-    from spacap3d_amd.linear import bf3_pieces
-    Wp = bf3_pieces(W)
-    check(lib.spacap_decode_word_f32(x.data_ptr(), Wp.data_ptr(), b.data_ptr(), R, V, lut.data_ptr(), scale, pe.data_ptr(), ys.data_ptr(), 5, 2,
-                                     xn.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream), "spacap_decode_word_f32")
-    word = ys[:, 2]
-    assert int(word[0]) == 3 and bool((ys[:, [0, 1, 3, 4]] == -1).all())
-    logits = x.double() @ W.double().t() + b.double()
-    best = logits.max(1).values
-    chosen = logits.gather(1, word.view(-1, 1)).squeeze(1)
-    assert float((best - chosen).max()) < 1e-4 * float(logits.abs().max())
-    assert float((word == logits.argmax(1)).double().mean()) > 0.995
-    assert torch.allclose(xn, lut[word] * scale + pe, rtol=0, atol=1e-5)
 
 
 @pytest.mark.parametrize("R,dff,p", [(2048, 2048, 0.0), (1000, 256, 0.0), (2048, 2048, 0.1)])

@@ -1,8 +1,8 @@
 """Device time of caption decoding at cfg2's decode shape (8 scenes x 256 proposals = 2 048 sequences, 31 words, V = 3 001,
 6 decoder layers, d_ff 2 048), one JSON line each, in ONE run so that the numbers share a device state:
 
-* ``tf_layer.greedy_decode`` -- the yardstick: today's greedy loop;
-* ``tf_layer.beam_decode`` for W = 1, 3, 5 (csrc/beam_search.hip).
+* ``caption_decode.greedy_decode`` -- the yardstick: today's greedy loop;
+* ``caption_decode.beam_decode`` for W = 1, 3, 5 (csrc/caption_decode.hip).
 
 Each decode is warmed up, captured in a graph and replayed between two HIP events (no host work inside); median of five
 groups.  Random weights and indicator rows: the time does not depend on the values (no step reads anything back).
@@ -24,7 +24,7 @@ def main():
     p.add_argument("--widths", default="1,3,5")
     a = p.parse_args()
     import torch
-    from spacap3d_amd import tf_layer
+    from spacap3d_amd import caption_decode
     from spacap3d_amd.spacapnet import build_default
     dev = "cuda:0"
     torch.manual_seed(0)
@@ -34,14 +34,14 @@ def main():
     sos, eos = cap.word_to_idx["sos"], cap.word_to_idx["eos"]
     R = B * K
     indicator = torch.randn(R, 128, device=dev)
-    assert tf_layer.decode_supported(m.decoder.layers, indicator, N_WORDS)
+    assert caption_decode.decode_supported(m.decoder.layers, indicator, N_WORDS)
     shape = {"sequences": R, "words": N_WORDS, "V": V, "layers": LAYERS, "iters": a.iters}
     with torch.no_grad():
-        us, ys = replay_us(lambda: tf_layer.greedy_decode(m.decoder, m.generator, embed, pos.pe, indicator, sos, N_WORDS), a.iters, settle=2)
+        us, ys = replay_us(lambda: caption_decode.greedy_decode(m.decoder, m.generator, embed, pos.pe, indicator, sos, N_WORDS), a.iters, settle=2)
         greedy = us
         print(json.dumps(dict(shape, what="greedy_decode", device_ms=round(us / 1e3, 3))), flush=True)
         for W in (int(w) for w in a.widths.split(",")):
-            us, out = replay_us(lambda: tf_layer.beam_decode(m.decoder, m.generator, embed, pos.pe, indicator, sos, eos, N_WORDS, W),
+            us, out = replay_us(lambda: caption_decode.beam_decode(m.decoder, m.generator, embed, pos.pe, indicator, sos, eos, N_WORDS, W),
                                 a.iters, settle=2)
             same = float((out[0] == ys).float().mean())
             print(json.dumps(dict(shape, what="beam_decode", W=W, device_ms=round(us / 1e3, 3), times_greedy=round(us / greedy, 2),

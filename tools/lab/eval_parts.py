@@ -2,21 +2,21 @@
 import time, torch, sys
 sys.path.insert(0, "/root/repo")
 import bench as B
-from spacap3d_amd import synthetic as S, tf_layer
+from spacap3d_amd import caption_decode, synthetic as S
 from spacap3d_amd.spacapnet import build_default
 dev = torch.device("cuda", 0)
 cfg = B.CFG["cfg2"]
 torch.manual_seed(0)
 model = build_default(input_feature_dim=S.num_extra_channels(**cfg["feats"]), num_proposal=cfg["proposals"], **cfg["transformer"]).to(dev).eval()
 data = B.synthetic_batch(cfg["batch"], cfg["n_points"], dev, seed=1000, **cfg["feats"])
-orig = tf_layer.greedy_decode
+orig = caption_decode.greedy_decode
 times = []
 def timed(*a, **k):
     torch.cuda.synchronize(); t0 = time.perf_counter()
     r = orig(*a, **k)
     torch.cuda.synchronize(); times.append((time.perf_counter() - t0) * 1e3)
     return r
-tf_layer.greedy_decode = timed
+caption_decode.greedy_decode = timed
 for g in (False,):
     times.clear()
     with torch.no_grad():
