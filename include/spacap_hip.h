@@ -1055,6 +1055,42 @@ int spacap_dense_caption_select(const uint8_t *valid, const float *obj_prob, con
                                 float *score, int32_t *cls, double *corners, int32_t *out_tokens, int32_t *length,
                                 spacap_stream_t stream);
 
+/* ---- multiview image features projected onto scene points (replaces lib/projection.py:189-260 under the frame loops of
+ * scripts/project_multiview_features.py:190-222 and scripts/project_multiview_labels.py:303-356; csrc/multiview.hip) ------- */
+
+/* What the three entry points below share.  points f32 [N,3] (world space), depth f32 [F,H,W] in metres, pose f32 [F,4,4]
+ * (camera_to_world, row-major), the pinhole model fx, fy, cx, cy, the depth range and the depth accuracy (f32 as the reference
+ * rounds them), corners: 24 f32 ON THE HOST, read during the call -- the eight camera-space frustum corners [8,3] at pixel
+ * centres (0,0), (W-1,0), (W-1,H-1), (0,H-1), first at depth_min, then at depth_max.  A point maps to pixel v*W + u of a frame
+ * when it passes the reference's rounded six-plane frustum test, projects (round half to even) into the image, and the depth
+ * map agrees with its camera z within `accuracy`; world_to_camera is the f64 cofactor inverse of the pose rounded to f32, and
+ * a frame whose pose or inverse is not finite maps nothing.  workspace: spacap_multiview_workspace_bytes(F) bytes on the
+ * device, written and read by the call.  H * W <= 6656.  N = 0 or F = 0 is a no-op.  No atomics, no host synchronisation;
+ * frames are applied in ascending order, so the calls of a scene may split its frames any way. */
+size_t spacap_multiview_workspace_bytes(int F);
+
+/* The projection map: map i32 [F,N] = the pixel index of point n in frame f, or -1. */
+int spacap_multiview_map_f32(const float *points, int N, const float *depth, const float *pose, int F, int H, int W, float fx,
+                             float fy, float cx, float cy, float depth_min, float depth_max, float accuracy, const float *corners,
+                             void *workspace, size_t workspace_bytes, int32_t *map, spacap_stream_t stream);
+
+/* Feature aggregation into acc f32 [N,C], IN/OUT (zeros before a scene's first call).  feats f32 [F,H*W,C], pixel-major.
+ * A frame covers a point when the point maps and the pixel's C-vector is not all-zero.  mode 0 (max): an all-zero accumulator
+ * row takes the vector, any other row the element-wise maximum; mode 1 (first): an all-zero row takes the vector.
+ * 1 <= C <= 256. */
+int spacap_multiview_features_f32(const float *points, int N, const float *depth, const float *pose, int F, int H, int W,
+                                  float fx, float fy, float cx, float cy, float depth_min, float depth_max, float accuracy,
+                                  const float *corners, const float *feats, int C, int mode, void *workspace,
+                                  size_t workspace_bytes, float *acc, spacap_stream_t stream);
+
+/* Label voting.  labels i32 [F,H*W]; 0 and anything outside 1..63 does not vote.  state u32 [N,64], IN/OUT (zeros before a
+ * scene's first call): [n,0] = distinct labels seen, [n,l] = 0 or (count << 6) | (63 - order of first appearance).
+ * voted i32 [N] = the most frequent label so far, ties to the one seen first, 0 when there is none; written on every call. */
+int spacap_multiview_vote_i32(const float *points, int N, const float *depth, const float *pose, int F, int H, int W, float fx,
+                              float fy, float cx, float cy, float depth_min, float depth_max, float accuracy, const float *corners,
+                              const int32_t *labels, void *workspace, size_t workspace_bytes, uint32_t *state, int32_t *voted,
+                              spacap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,10 @@ SIGNATURES = {
     "spacap_caption_score_f64": (_i, [_p, _p, _i, _p, ctypes.c_int64, _p, _p, ctypes.c_int64, _p, _p, _p, _p,
                                       ctypes.c_double, _p, _p, _p, _p]),
     "spacap_dense_caption_select": (_i, [_p] * 5 + [_i] * 5 + [_p] * 7 + [_p]),
+    "spacap_multiview_workspace_bytes": (ctypes.c_size_t, [_i]),
+    "spacap_multiview_map_f32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, ctypes.c_size_t, _p, _p]),
+    "spacap_multiview_features_f32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, _i, _i, _p, ctypes.c_size_t, _p, _p]),
+    "spacap_multiview_vote_i32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, _p, ctypes.c_size_t, _p, _p, _p]),
     "spacap_stream_delay": (_i, [_i, _p]),
     "spacap_stream_wait_ge": (_i, [_p, _l, _i, _p, _p]),
     "spacap_stream_signal": (_i, [_p, _p, _p]),

@@ -104,11 +104,16 @@ class DeviceSceneDataset:
     def add_scene(self, scene_id, vert, ins, sem, bbox, x=None, y=None, z=None, multiview=None):
         """Arrays as the reference loads them (lib/dataset.py:197-212): vert (N,9) f32, ins / sem (N,), bbox (M,8)
         [centre, size, nyu40 id, object id], x / y / z (M,M) relation classes; ``multiview``: the scene's (N,128)
-        float32 rows of the multiview database (required with use_multiview)."""
+        float32 rows of the multiview database (required with use_multiview) -- a host array, or a float32 tensor on this
+        dataset's device (``multiview.MultiviewProjector.project_features``), which is kept without a host round trip."""
         vert = np.asarray(vert)
+        mv_on_device = isinstance(multiview, torch.Tensor) and multiview.is_cuda
         if self.use_multiview:
-            if multiview is None or tuple(np.shape(multiview)) != (vert.shape[0], 128):
+            shape = tuple(multiview.shape) if mv_on_device else (None if multiview is None else tuple(np.shape(multiview)))
+            if shape != (vert.shape[0], 128):
                 raise ValueError("use_multiview needs the scene's (N, 128) multiview rows")
+            if mv_on_device and multiview.dtype != torch.float32:
+                raise ValueError("multiview rows on a device must be float32")
         pc = vert[:, 0:3]
         if self.use_normal:
             pc = np.concatenate([pc, vert[:, 6:9]], 1)
@@ -137,7 +142,8 @@ class DeviceSceneDataset:
         if self.color_renorm == "per_access":   # the raw copy only exists where reset_colors() needs it (~1 GB over all of ScanNet)
             self._scenes[-1]["color0"] = torch.as_tensor(np.ascontiguousarray(vert[:, 3:6], dtype=np.float32)).to(d)
         if self.use_multiview:
-            self._scenes[-1]["multiview"] = torch.as_tensor(np.ascontiguousarray(multiview, dtype=np.float32)).to(d)
+            self._scenes[-1]["multiview"] = multiview.to(d).contiguous() if mv_on_device else \
+                torch.as_tensor(np.ascontiguousarray(multiview, dtype=np.float32)).to(d)
         self._tables = None
 
     def load_scene(self, root, scene_id, multiview_db=None):
