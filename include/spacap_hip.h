@@ -1091,6 +1091,53 @@ int spacap_multiview_vote_i32(const float *points, int N, const float *depth, co
                               const int32_t *labels, void *workspace, size_t workspace_bytes, uint32_t *state, int32_t *voted,
                               spacap_stream_t stream);
 
+/* ---- the ENet image encoder: colour frames to pixel-major feature maps (replaces the encoder of lib/enet.py as
+ * scripts/compute_multiview_features.py runs it: create_enet without its classifier, eval(); csrc/enet.hip) ----------------- */
+
+/* Activations are f32, pixel-major: [B][h w][C].  The encoder is the initial block (3 -> 16 channels, the map halves) and 22
+ * bottlenecks: stage 1 = down 16 -> 64 and four regular ones; stage 2 = down 64 -> 128 and regular 1, dilated 2, asymmetric,
+ * dilated 4, regular 1, dilated 8, asymmetric, dilated 16; stage 3 = those eight again.  A down-sampling bottleneck halves the
+ * map rounding down.  Output: [B][(H/8) (W/8)][128], which spacap_multiview_features_f32 reads as `feats`.
+ *
+ * params: BatchNorm (eps 0.001, running statistics) and the reference's eval-mode dropout factor 1 - p are folded into the
+ * convolutions on the host (spacap3d_amd/enet.py); a layer is  y = PReLU_a(conv_w(x) + b [+ skip]).  The packed buffer, f32,
+ * 16-byte aligned, spacap_enet_param_floats() long:
+ *   initial block, 480 floats: w[16][27] (output channel, then (ky*3 + kx)*3 + input channel; rows 13..15 unused), b[16]
+ *     (13..15: the additive term of the three pooled channels), scale[16] (13..15: their multiplier, the others unused),
+ *     PReLU slope[16];
+ *   then per bottleneck, in network order, spacap_enet_bottleneck_param_floats(kind, cin, cout) floats, M = cout / 4:
+ *     w1[M][T1 cin], b1[M], a1[M]     the reduce: T1 = 1, or 4 taps (ky*2 + kx) of the 2x2 stride-2 conv when down-sampling;
+ *     w2[M][T2 M], b2[M], a2[M]       the middle: T2 = 9 taps (ky*3 + kx), or the 25 taps (ky*5 + kx) of the 5x5 conv that
+ *                                     equals the asymmetric 1x5 / 5x1 pair, W[o,i,ky,kx] = sum_m W5x1[o,m,ky] W1x5[m,i,kx];
+ *     w3[cout][M], b3[cout], a3[cout] the expand and the PReLU behind the sum with the skip branch;
+ *     every contraction index is tap-major, input-channel-minor; a = PReLU slopes.
+ * kind: 0 regular / dilated (64 -> 64, 128 -> 128), 1 asymmetric (128 -> 128), 2 down-sampling (16 -> 64, 64 -> 128).
+ * No atomics, no host synchronisation, a straight line of launches on `stream`; a pixel's value does not depend on B. */
+size_t spacap_enet_param_floats(void);
+size_t spacap_enet_bottleneck_param_floats(int kind, int cin, int cout);   /* 0 when the shape is not supported */
+
+/* Bytes of device workspace spacap_enet_encode_* needs for B images of H x W (0 when the sizes are not supported). */
+size_t spacap_enet_workspace_bytes(int B, int H, int W);
+
+/* The initial block alone: images f32 [B,H,W,3] (pixel-major, normalised) -> out f32 [B,(H/2)(W/2),16]; params: the first
+ * 480 floats of the packed buffer.  H and W even and >= 8; B = 0 is a no-op. */
+int spacap_enet_initial_f32(const float *images, int B, int H, int W, const float *params, float *out, spacap_stream_t stream);
+
+/* One bottleneck: in f32 [B,h w,cin] -> out f32 [B,ho wo,cout], (ho, wo) = (h / 2, w / 2) rounded down for kind 2, else (h, w).
+ * params: this bottleneck's floats as laid out above.  dilation applies to kind 0.  workspace: B * ho * wo * (cout / 4) floats,
+ * written and read by the call.  in != out; in, params, workspace and out 16-byte aligned.  Two launches. */
+int spacap_enet_bottleneck_f32(const float *in, int B, int h, int w, int cin, int cout, int kind, int dilation,
+                               const float *params, void *workspace, size_t workspace_bytes, float *out, spacap_stream_t stream);
+
+/* The whole encoder: images f32 [B,H,W,3] pixel-major, normalised -> out f32 [B,(H/8)(W/8),128].  45 launches. */
+int spacap_enet_encode_f32(const float *images, int B, int H, int W, const float *params, size_t n_params, void *workspace,
+                           size_t workspace_bytes, float *out, spacap_stream_t stream);
+
+/* The same from u8 [B,H,W,3]: x = (u8 / 255 - mean[c]) / std[c], in f32 and in that order, inside the initial block. */
+int spacap_enet_encode_u8(const uint8_t *images, int B, int H, int W, float mean0, float mean1, float mean2, float std0,
+                          float std1, float std2, const float *params, size_t n_params, void *workspace, size_t workspace_bytes,
+                          float *out, spacap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,13 @@ SIGNATURES = {
     "spacap_multiview_map_f32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, ctypes.c_size_t, _p, _p]),
     "spacap_multiview_features_f32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, _i, _i, _p, ctypes.c_size_t, _p, _p]),
     "spacap_multiview_vote_i32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, _p, ctypes.c_size_t, _p, _p, _p]),
+    "spacap_enet_param_floats": (ctypes.c_size_t, []),
+    "spacap_enet_bottleneck_param_floats": (ctypes.c_size_t, [_i, _i, _i]),
+    "spacap_enet_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "spacap_enet_initial_f32": (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    "spacap_enet_bottleneck_f32": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, ctypes.c_size_t, _p, _p]),
+    "spacap_enet_encode_f32": (_i, [_p, _i, _i, _i, _p, ctypes.c_size_t, _p, ctypes.c_size_t, _p, _p]),
+    "spacap_enet_encode_u8": (_i, [_p, _i, _i, _i] + [_f] * 6 + [_p, ctypes.c_size_t, _p, ctypes.c_size_t, _p, _p]),
     "spacap_stream_delay": (_i, [_i, _p]),
     "spacap_stream_wait_ge": (_i, [_p, _l, _i, _p, _p]),
     "spacap_stream_signal": (_i, [_p, _p, _p]),
