@@ -1138,6 +1138,36 @@ int spacap_enet_encode_u8(const uint8_t *images, int B, int H, int W, float mean
                           float std1, float std2, const float *params, size_t n_params, void *workspace, size_t workspace_bytes,
                           float *out, spacap_stream_t stream);
 
+/* ---- ScanNet scene preparation: normals, labels, boxes, relations (replaces data/scannet/load_scannet_data.py::export with
+ * scannet_utils.compute_normal, and generate_spatiality_label.py with save_npy; csrc/scene_export.hip) -------- */
+
+/* xyz f32 [N,3]; faces i32 [F,3] with indices in [0, N); 0 <= N < 2^24 (N = 0 is a no-op), F >= 0.  Every result is numpy's,
+ * bit for bit; all outputs are deterministic.  The caller validates the indices (face corners, segment ids, the values of the
+ * tables); an index outside its table is skipped, not followed.  workspace: device memory of the size the query below returns
+ * (with M = 0 for the normals alone), initialised by the call itself.  No host synchronisation. */
+size_t spacap_scene_export_workspace_bytes(int N, int M);
+
+/* Vertex normals f32 [N,3]: per face cross(v1 - v0, v2 - v0) / (|.| + 1e-8f); per vertex and corner slot the LAST face of the
+ * file that holds the vertex in that slot contributes (numpy's buffered fancy-indexed "+="), slots added in order 0, 1, 2 onto
+ * zero and normalised by the same formula.  Three launches. */
+int spacap_scene_normals_f32(const float *xyz, int N, const int32_t *faces, int F, void *workspace, size_t workspace_bytes,
+                             float *normals, spacap_stream_t stream);
+
+/* Relation classes rel i32 [3,M,M] (x, y, z; 0 = forward / up, 1 = same, 2 = behind / below) of the f64 boxes bbox [M,8] =
+ * [centre, size, ...], f64 arithmetic in the reference's expression order.  0 <= M <= 1024 (M = 0 is a no-op).  One launch. */
+int spacap_scene_relations_f64(const double *bbox, int M, int32_t *rel, spacap_stream_t stream);
+
+/* The whole export.  rgb f32 [N,3]; seg i32 [N] = the segment of every vertex; seg_ins / seg_sem i32 [S] = the instance id
+ * (objectId + 1, 0 = none, at most M) and the label id of every segment; box_label i32 [M]; axis_align: 16 doubles ON THE HOST
+ * (row-major 4 x 4) or NULL.  Out: vert / aligned_vert f32 [N,9] (xyz, rgb, normal; aligned xyz = f32(((x a0 + y a1) + z a2)
+ * + a3) in f64, normals not rotated), ins / sem i32 [N], bbox / aligned_bbox f64 [M,8] = [centre, size, box_label, m] with
+ * centre = (min + max) / 2 and size = max - min in f32, an instance without a vertex all zero; rel i32 [3,M,M] of aligned_bbox.
+ * 1 <= M <= 1024, S >= 1.  Five launches. */
+int spacap_scene_export_f32(const float *xyz, const float *rgb, int N, const int32_t *faces, int F, const int32_t *seg,
+                            const int32_t *seg_ins, const int32_t *seg_sem, int S, const int32_t *box_label, int M,
+                            const double *axis_align, void *workspace, size_t workspace_bytes, float *vert, float *aligned_vert,
+                            int32_t *ins, int32_t *sem, double *bbox, double *aligned_bbox, int32_t *rel, spacap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

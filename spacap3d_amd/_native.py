@@ -100,6 +100,10 @@ SIGNATURES = {
     "spacap_multiview_map_f32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, ctypes.c_size_t, _p, _p]),
     "spacap_multiview_features_f32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, _i, _i, _p, ctypes.c_size_t, _p, _p]),
     "spacap_multiview_vote_i32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, _p, ctypes.c_size_t, _p, _p, _p]),
+    "spacap_scene_export_workspace_bytes": (ctypes.c_size_t, [_i, _i]),
+    "spacap_scene_normals_f32": (_i, [_p, _i, _p, _i, _p, ctypes.c_size_t, _p, _p]),
+    "spacap_scene_relations_f64": (_i, [_p, _i, _p, _p]),
+    "spacap_scene_export_f32": (_i, [_p, _p, _i, _p, _i, _p, _p, _p, _i, _p, _i, _p, _p, ctypes.c_size_t] + [_p] * 8),
     "spacap_enet_param_floats": (ctypes.c_size_t, []),
     "spacap_enet_bottleneck_param_floats": (ctypes.c_size_t, [_i, _i, _i]),
     "spacap_enet_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),

@@ -105,15 +105,15 @@ class DeviceSceneDataset:
         """Arrays as the reference loads them (lib/dataset.py:197-212): vert (N,9) f32, ins / sem (N,), bbox (M,8)
         [centre, size, nyu40 id, object id], x / y / z (M,M) relation classes; ``multiview``: the scene's (N,128)
         float32 rows of the multiview database (required with use_multiview) -- a host array, or a float32 tensor on this
-        dataset's device (``multiview.MultiviewProjector.project_features``), which is kept without a host round trip."""
+        dataset's device (``multiview.MultiviewProjector.project_features``), which is kept without a host round trip.
+        ``vert`` may also be a float32 tensor on this dataset's device, with ``ins`` and ``sem`` integer tensors there
+        (``scene_export.export_scene``): the per-vertex data then makes no host round trip either, and the scene keeps,
+        bit for bit, what the host arrays of the same values would have given it (``bbox`` / ``x`` / ``y`` / ``z`` may be
+        tensors or arrays: they are tiny and go through the host)."""
+        if isinstance(vert, torch.Tensor) and vert.is_cuda:
+            return self._add_scene_device(scene_id, vert, ins, sem, bbox, x, y, z, multiview)
         vert = np.asarray(vert)
-        mv_on_device = isinstance(multiview, torch.Tensor) and multiview.is_cuda
-        if self.use_multiview:
-            shape = tuple(multiview.shape) if mv_on_device else (None if multiview is None else tuple(np.shape(multiview)))
-            if shape != (vert.shape[0], 128):
-                raise ValueError("use_multiview needs the scene's (N, 128) multiview rows")
-            if mv_on_device and multiview.dtype != torch.float32:
-                raise ValueError("multiview rows on a device must be float32")
+        mv = self._multiview_rows(multiview, vert.shape[0])
         pc = vert[:, 0:3]
         if self.use_normal:
             pc = np.concatenate([pc, vert[:, 6:9]], 1)
@@ -123,14 +123,7 @@ class DeviceSceneDataset:
         if int(np.asarray(ins).max(initial=0)) >= self.max_instances:
             raise ValueError("instance label >= max_instances")
         d = self.device
-        bbox = np.asarray(bbox, dtype=np.float64)
-        nb = min(bbox.shape[0], MAX_NUM_OBJ)
-        box8 = np.zeros((MAX_NUM_OBJ, 8))
-        box8[:nb] = bbox[:nb]
-        rel = np.zeros((3, MAX_NUM_OBJ, MAX_NUM_OBJ), dtype=np.int64)
-        for k, r in enumerate((x, y, z)):
-            if r is not None:
-                rel[k, :nb, :nb] = np.asarray(r)[:nb, :nb]
+        nb, box8, rel = _box_tables(bbox, x, y, z)
         self._scene_index[scene_id] = len(self._scenes)
         self._scenes.append({
             "feat": torch.as_tensor(np.ascontiguousarray(pc, dtype=np.float32)).to(d),
@@ -141,9 +134,79 @@ class DeviceSceneDataset:
         })
         if self.color_renorm == "per_access":   # the raw copy only exists where reset_colors() needs it (~1 GB over all of ScanNet)
             self._scenes[-1]["color0"] = torch.as_tensor(np.ascontiguousarray(vert[:, 3:6], dtype=np.float32)).to(d)
-        if self.use_multiview:
-            self._scenes[-1]["multiview"] = multiview.to(d).contiguous() if mv_on_device else \
-                torch.as_tensor(np.ascontiguousarray(multiview, dtype=np.float32)).to(d)
+        if mv is not None:
+            self._scenes[-1]["multiview"] = mv
+        self._tables = None
+
+    def _multiview_rows(self, multiview, n):
+        """The scene's (n, 128) multiview rows as the float32 tensor it keeps on the device, checked; None without use_multiview."""
+        if not self.use_multiview:
+            return None
+        on_device = isinstance(multiview, torch.Tensor) and multiview.is_cuda
+        shape = tuple(multiview.shape) if on_device else (None if multiview is None else tuple(np.shape(multiview)))
+        if shape != (n, 128):
+            raise ValueError("use_multiview needs the scene's (N, 128) multiview rows")
+        if on_device and multiview.dtype != torch.float32:
+            raise ValueError("multiview rows on a device must be float32")
+        return multiview.to(self.device).contiguous() if on_device else \
+            torch.as_tensor(np.ascontiguousarray(multiview, dtype=np.float32)).to(self.device)
+
+    def _add_scene_device(self, scene_id, vert, ins, sem, bbox, x, y, z, multiview):
+        """add_scene for per-vertex tensors on the device.  Every tensor equals the host path's: the same float32 / float64
+        operations in the same order.  The floor of the height channel is numpy's own 0.99th percentile: it depends on the
+        number of values and on the two order statistics around the quantile's position only, so four sorted values around
+        it are read back and ``np.percentile`` runs on a stand-in of the same length that has them at the same ranks.
+        One caveat: where the values at those ranks tie at +0.0 and -0.0 (a vertex at z == -0.0 exactly), numpy's partition
+        and the device's selection may order the two zeros differently, and the floor's sign of zero with them."""
+        d = self.device
+        if vert.dim() != 2 or vert.shape[1] != 9 or vert.dtype != torch.float32:
+            raise ValueError("vert on a device must be an (N, 9) float32 tensor")
+        n = int(vert.shape[0])
+        for name, t in (("ins", ins), ("sem", sem)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda) or t.is_floating_point() or tuple(t.shape) != (n,):
+                raise ValueError(f"with vert on a device, {name} must be an (N,) integer tensor on it")
+        mv = self._multiview_rows(multiview, n)
+        vert, ins, sem = vert.to(d), ins.to(d), sem.to(d)
+        cols = [vert[:, 0:3]]
+        if self.use_normal:
+            cols.append(vert[:, 6:9])
+        if self.use_height:
+            height_of = vert[:, 2]
+            lo = int(math.floor((n - 1) * 0.0099))           # the rank below the quantile's position, give or take one
+            i0, k = max(lo - 1, 0), min(n, lo + 3)
+            ranks = torch.topk(height_of, k, largest=False, sorted=True).values[i0:].cpu().numpy()
+            stand_in = np.empty(n, dtype=np.float32)
+            stand_in[:i0], stand_in[i0:k], stand_in[k:] = ranks[0], ranks, ranks[-1]
+            floor = np.percentile(stand_in, 0.99)
+            # The host path computes ``pc[:, 2] - floor`` with numpy's promotion rules.  np.percentile of float32 data
+            # returns a float32 scalar in numpy 2.2, so the difference is float32; a numpy whose percentile returns a
+            # float64 scalar keeps it float32 under 1.x's value-based casting but makes it float64 -- rounded to float32
+            # when the rows are stored -- under NEP 50 (numpy >= 2).  Ask the installed numpy which of the two it does:
+            if (np.zeros(1, dtype=np.float32) - floor).dtype == np.float32:
+                height = height_of - float(floor)
+            else:
+                height = (height_of.double() - float(floor)).float()
+            cols.append(height.unsqueeze(1))
+        if n and int(ins.max()) >= self.max_instances:
+            raise ValueError("instance label >= max_instances")
+        nb, box8, rel = _box_tables(_host(bbox), *(None if r is None else _host(r) for r in (x, y, z)))
+        raw = vert[:, 3:6].contiguous()
+        col = raw
+        if self.use_color and self.color_renorm == "once":
+            col = ((raw.double() - self._mean_rgb) / 256.0).float()
+        nyu = torch.tensor(NYU40IDS, dtype=torch.int64, device=d)
+        self._scene_index[scene_id] = len(self._scenes)
+        self._scenes.append({
+            "feat": torch.cat(cols, 1).contiguous(),
+            "color": col,
+            "ins": ins.to(torch.int32, copy=True).contiguous(),
+            "isobj": torch.isin(sem.long(), nyu).to(torch.uint8),
+            "n": n, "nb": nb, "box8": box8, "rel": rel,
+        })
+        if self.color_renorm == "per_access":
+            self._scenes[-1]["color0"] = raw.clone()
+        if mv is not None:
+            self._scenes[-1]["multiview"] = mv
         self._tables = None
 
     def load_scene(self, root, scene_id, multiview_db=None):
@@ -372,6 +435,23 @@ class DeviceSceneDataset:
             for k in ("lang_feat", "lang_ids", "lang_label", "lang_len"):
                 d[k] = t[k][idx]
         return d
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+
+
+def _box_tables(bbox, x, y, z):
+    """A scene's box rows and relation classes padded to MAX_NUM_OBJ: (nb, box8 (128, 8) f64, rel (3, 128, 128) i64)."""
+    bbox = np.asarray(bbox, dtype=np.float64)
+    nb = min(bbox.shape[0], MAX_NUM_OBJ)
+    box8 = np.zeros((MAX_NUM_OBJ, 8))
+    box8[:nb] = bbox[:nb]
+    rel = np.zeros((3, MAX_NUM_OBJ, MAX_NUM_OBJ), dtype=np.int64)
+    for k, r in enumerate((x, y, z)):
+        if r is not None:
+            rel[k, :nb, :nb] = np.asarray(r)[:nb, :nb]
+    return nb, box8, rel
 
 
 def _rotate_aligned_boxes(tb, R, axis):
