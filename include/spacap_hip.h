@@ -289,6 +289,34 @@ int spacap_relation_fused_fwd_f32(const float *P, const float *U, const float *b
 int spacap_relation_fused_bwd_f32(const float *dpred, const float *hid2, const float *P, const float *U, const float *b1,
                                   const float *W2, const float *W3, int B, int K, int nparts, int zslots, float *dP,
                                   float *dU, float *part, spacap_stream_t stream);
+/* The same backward over the proposal pairs that carry a gradient.  The relation loss weights pair (i, j) by s_i s_j (both
+ * proposals positive and assigned), so dpred is zero outside (selected i) x (selected j); the selection is taken from dpred
+ * itself and the entry is correct for ANY dpred.  Query row (b, i) is active iff some dpred[b,i,:,:] != 0, key column
+ * (b, j) iff some dpred[b,:,j,:] != 0 (-0 is inactive, NaN active).  Per scene the active rows and columns are compacted
+ * into ascending lists, each padded to a multiple of 8 with the first inactive indices (ascending), and the tile loop of
+ * spacap_relation_fused_bwd_f32 runs over (8 list rows) x (8 list columns) tiles: n_sel^2 work instead of K^2.  dP outside
+ * the visited tiles, dU of unvisited key columns and the partials of idle workgroups are written as exact zeros; every
+ * byte of dP, dU [zslots, B,K,H,C] and part is written on every call.  Three launches on `stream` (scan of dpred + zero
+ * fill, compaction, backward), fixed grids, nothing read back: capturable, and a replay follows the dpred of the replay.
+ * While the 8-aligned (query block, key block) tiles that hold an active pair number no more than the tiles over the lists
+ * (everything active) or at most 1/16 of all tiles (a handful of selected proposals per scene), the kernel instead walks the
+ * dense kernel's own tiles with its partition and slots and skips the inactive ones: the results (dP, the sum of dU over
+ * its slots, the sum of part over nparts) are then bit for bit those of spacap_relation_fused_bwd_f32 at the same (B, K,
+ * nparts, zslots).  Over the lists the products per pair are the same and the order of the sums is another.
+ * zslots >= spacap_relation_fused_sel_zsplit(B, K, nparts) (>= 3 and >= spacap_relation_fused_zsplit).
+ * workspace: spacap_relation_fused_sel_workspace_bytes(B, K) bytes, 8-byte aligned, as int32 words
+ *     cnt  [B][4]  at word 0            {active rows, active columns, row list length / 8, column list length / 8}
+ *     qi   [B][K]  at word 4 B          the row list of scene b in its first 8 cnt[b][2] entries (the rest is not written)
+ *     kj   [B][K]  at word 4 B + B K    the column list, likewise
+ *     then 2 B K words of flags, B K ceil(K / 64) 64-bit column masks and B (2 + K / 4) words of block counts and flags (scratch).
+ * spacap_relation_fused_sel_lists_f32 is the first two launches alone (lists into the workspace, zeros into dP and dU). */
+int spacap_relation_fused_sel_zsplit(int B, int K, int nparts);
+size_t spacap_relation_fused_sel_workspace_bytes(int B, int K);
+int spacap_relation_fused_sel_lists_f32(const float *dpred, int B, int K, int zslots, float *dP, float *dU, void *workspace,
+                                        spacap_stream_t stream);
+int spacap_relation_fused_bwd_sel_f32(const float *dpred, const float *hid2, const float *P, const float *U, const float *b1,
+                                      const float *W2, const float *W3, int B, int K, int nparts, int zslots, float *dP,
+                                      float *dU, float *part, void *workspace, spacap_stream_t stream);
 
 /* ---- decoder input of the captioner's training step (replaces models/transformer_captioner.py:350-367, 246-249, 129-137,
  * 150-161, 193-199 as separate tensor operations) ---------------------------------------------------------------------------

@@ -69,6 +69,10 @@ SIGNATURES = {
     "spacap_relation_fused_part_floats": (_i, []),
     "spacap_relation_fused_fwd_f32": (_i, [_p] * 7 + [_i, _i, _p, _p, _p]),
     "spacap_relation_fused_bwd_f32": (_i, [_p] * 7 + [_i, _i, _i, _i, _p, _p, _p, _p]),
+    "spacap_relation_fused_sel_zsplit": (_i, [_i, _i, _i]),
+    "spacap_relation_fused_sel_workspace_bytes": (ctypes.c_size_t, [_i, _i]),
+    "spacap_relation_fused_sel_lists_f32": (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
+    "spacap_relation_fused_bwd_sel_f32": (_i, [_p] * 7 + [_i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "spacap_caption_prep_fwd_f32": (_i, [_p] * 7 + [_i] * 5 + [_f, _u64, _p] + [_p] * 7 + [_p]),
     "spacap_caption_prep_bwd_f32": (_i, [_p] * 3 + [_i] * 5 + [_f, _u64, _p, _p, _p, _p]),
     "spacap_conv1x1_cm_supported": (_i, [_i, _i, _l]),

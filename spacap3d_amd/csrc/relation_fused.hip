@@ -13,6 +13,9 @@
 //             dhid1 = dz2 W2; dz1 = dhid1 * [hid1 > 0]; then layer 1's gradients from the tile: dP[b,h,i,j] =
 //             dz1 . U[b,j,h,:] (stored), dU[b,j,h,:] += P dz1 (registers, written once at the end); the bias sums ride the
 //             same products as a column of ones; all parameter sums leave as per-workgroup partials (fixed order, no atomics).
+//   backward over the selected pairs (spacap_relation_fused_bwd_sel_f32): dpred is zero unless both proposals of a pair are
+//             selected by the relation loss; the active query rows and key columns are found from dpred, compacted into lists
+//             and the same tile body runs over (8 list rows) x (8 list columns): n_sel^2 work instead of K^2.
 // Every product, the small per-key ones included (block-diagonal operands, two key columns per 16-row tile), runs on the
 // matrix cores: the backward has one wave per SIMD, so VALU phases would leave the matrix pipe idle.
 // Arithmetic: the three 128 x 128 products (layer 2, dhid1, dW2: 94 % of the flops) as split-bf16, three bf16 pieces per
@@ -64,6 +67,14 @@ __device__ __forceinline__ void p_tile_request(const float *__restrict__ P, int 
   for (int e = 0; e < 2; ++e) {
     const int idx = threadIdx.x + 256 * e, h = idx >> 6, ii = (idx >> 3) & 7, jj = idx & 7;
     pp[e] = P[(((size_t)b * H + h) * K + i0 + ii) * K + j0 + jj];
+  }
+}
+// the same for a thread that knows its query row and key column (the selected backward: rows and columns come from lists)
+__device__ __forceinline__ void p_tile_request_at(const float *__restrict__ P, int b, int K, int qrow, int kcol, float *pp) {
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const int h = (threadIdx.x + 256 * e) >> 6;
+    pp[e] = P[(((size_t)b * H + h) * K + qrow) * K + kcol];
   }
 }
 __device__ __forceinline__ void p_tile_store(const float *pp, float *s_p) {
@@ -191,11 +202,38 @@ __global__ __launch_bounds__(256) void rel_fused_fwd_kernel(const float *__restr
   }
 }
 
-__global__ __launch_bounds__(256) void rel_fused_bwd_kernel(const float *__restrict__ dpred, const float *__restrict__ hid2,
-                                                            const float *__restrict__ P, const float *__restrict__ U,
-                                                            const float *__restrict__ b1, const float *__restrict__ W2,
-                                                            const float *__restrict__ W3, int B, int K, int Z,
-                                                            float *__restrict__ dP, float *__restrict__ dU, float *__restrict__ part) {
+// ---- the selected backward's workspace (int32 words; include/spacap_hip.h documents it): per-scene counts, the compacted
+// lists, the flags they are made from ------------------------------------------------------------------------------------
+__host__ __device__ inline size_t sel_cnt_off(int, int) { return 0; }                                        // [B][4]
+__host__ __device__ inline size_t sel_qi_off(int B, int) { return (size_t)4 * B; }                           // [B][K]
+__host__ __device__ inline size_t sel_kj_off(int B, int K) { return (size_t)4 * B + (size_t)B * K; }         // [B][K]
+__host__ __device__ inline size_t sel_rowflag_off(int B, int K) { return (size_t)4 * B + (size_t)2 * B * K; }   // [B][K]
+__host__ __device__ inline size_t sel_colflag_off(int B, int K) { return (size_t)4 * B + (size_t)3 * B * K; }   // [B][K]
+__host__ __device__ inline size_t sel_colbits_off(int B, int K) { return (size_t)4 * B + (size_t)4 * B * K; }   // 64-bit [B][K][NW]
+__host__ __device__ inline int sel_nw(int K) { return (K + 63) >> 6; }
+// per scene {active row blocks, active column blocks, row-block flags [K/8], column-block flags [K/8]}: 8-aligned blocks of
+// proposals that hold an active one (the tiles of the dense kernel that can be non-zero)
+__host__ __device__ inline size_t sel_blk_off(int B, int K) { return sel_colbits_off(B, K) + (size_t)2 * B * K * sel_nw(K); }
+__host__ __device__ inline int sel_blk_stride(int K) { return 2 + 2 * (K / 8); }
+__device__ __forceinline__ int clampi(int v, int hi) { return min(max(v, 0), hi); }
+
+// The backward of one workgroup.  SEL = false: all B K K pairs, a static partition of the (scene, key block, query block) units.
+// SEL = true, one of two walks, chosen from the counts in the workspace `ws` (rel_sel_scan_kernel, rel_sel_compact_kernel below):
+//   in place    the tiles, partition and dU slots of SEL = false, but only tiles whose query block and key block hold an active
+//               proposal are visited.  A tile without an active pair adds exact zeros to every sum, so the results are the
+//               bits of SEL = false.  Taken while it costs no more tiles than the lists (everything active) or at most 1/16
+//               of all tiles (a handful of selected proposals per scene).
+//   over lists  the units are (8 entries of the scene's query list) x (8 entries of its key list); rows of P, hid2, dpred, U
+//               and of dP, dU are addressed through the lists: n_sel^2 work where most 8-blocks hold a selected proposal.
+//               Workgroup g takes the units [g L, (g + 1) L), L = max(ceil(NU / G), ceil(NI_max / (Z - 1))): a key block
+//               (at most NI_max units) then meets at most Z workgroups.  Same products per pair, another summation order.
+// dP and dU outside the visited tiles are the caller's zeros (the scan kernel writes them).
+template <bool SEL>
+__device__ __forceinline__ void rel_bwd_body(const float *__restrict__ dpred, const float *__restrict__ hid2,
+                                             const float *__restrict__ P, const float *__restrict__ U,
+                                             const float *__restrict__ b1, const float *__restrict__ W2,
+                                             const float *__restrict__ W3, int B, int K, int Z, const int *__restrict__ ws,
+                                             float *__restrict__ dP, float *__restrict__ dU, float *__restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __bf16 *s_h1T = reinterpret_cast<__bf16 *>(smem_raw);                  // hid1 pieces, channel-major [3][128][LDR]
   __bf16 *s_zT = s_h1T + 3 * IMGT;                                       // dz2 pieces, channel-major; the same bytes later
@@ -206,7 +244,50 @@ __global__ __launch_bounds__(256) void rel_fused_bwd_kernel(const float *__restr
   const int jj = tid >> 5, c4 = tid & 31;
   // this workgroup's contiguous range of tile units (unit = (scene, key block, query block), query block fastest)
   const int NI = K / TI, NJ = K / TJ;
-  const long NU = (long)B * NJ * NI, u_beg = (long)blockIdx.x * NU / gridDim.x, u_end = ((long)blockIdx.x + 1) * NU / gridDim.x;
+  long NU = (long)B * NJ * NI, u_beg = (long)blockIdx.x * NU / gridDim.x, u_end = ((long)blockIdx.x + 1) * NU / gridDim.x;
+  long L = 0;          // SEL, not all active: the length of every workgroup's range
+  bool dense = true;   // the static partition above holds
+  const int *cnt = SEL ? ws + sel_cnt_off(B, K) : nullptr, *blk = SEL ? ws + sel_blk_off(B, K) : nullptr;
+  const int BS = sel_blk_stride(K);
+  if (SEL) {
+    // units, the longest query list and "everything active" over the scenes; every count clamped to what the lists can hold
+    long long nu = 0, tb = 0;   // tiles over the compacted lists; tiles of the dense kernel that hold an active pair
+    int nim = 0;
+    for (int s = tid; s < B; s += 256) {
+      const int ni = clampi(cnt[4 * s + 2], NI), nj = clampi(cnt[4 * s + 3], NJ);
+      nu += (long long)ni * nj;
+      nim = max(nim, ni);
+      tb += (long long)clampi(blk[(size_t)s * BS], NI) * clampi(blk[(size_t)s * BS + 1], NJ);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      nu += __shfl_xor(nu, m);
+      tb += __shfl_xor(tb, m);
+      nim = max(nim, __shfl_xor(nim, m));
+    }
+    long long *s_nu = reinterpret_cast<long long *>(s_x);
+    int *s_ni = reinterpret_cast<int *>(s_nu + 8);
+    if (lane == 0) s_nu[w] = nu, s_nu[4 + w] = tb, s_ni[w] = nim;
+    __syncthreads();
+    nu = (s_nu[0] + s_nu[1]) + (s_nu[2] + s_nu[3]);
+    tb = (s_nu[4] + s_nu[5]) + (s_nu[6] + s_nu[7]);
+    nim = max(max(s_ni[0], s_ni[1]), max(s_ni[2], s_ni[3]));
+    // In place (the dense kernel's tiles, partition and slots, inactive tiles skipped: the dense kernel's bits, since a tile
+    // without an active pair adds exact zeros) while that costs no more tiles than the lists (everything active) or at most
+    // 1/16 of the dense kernel; over the lists (fewer tiles, other summation order) beyond that.
+    dense = tb <= nu || tb * 16 <= NU;
+    if (!dense) {
+      NU = nu;
+      L = max((NU + gridDim.x - 1) / gridDim.x, (long)(nim + max(Z - 1, 1) - 1) / max(Z - 1, 1));
+      u_beg = min(NU, (long)blockIdx.x * L);
+      u_end = min(NU, ((long)blockIdx.x + 1) * L);
+    }
+    if (u_beg >= u_end) {   // nothing selected in this range: zero partial sums
+      float *po = part + (size_t)blockIdx.x * PART;
+      for (int idx = tid; idx < PART; idx += 256) po[idx] = 0.f;
+      return;
+    }
+  }
   // ---- operands that stay in registers for the whole launch ------------------------------------------------------------
   float bA[8], w3A[8][3];
 #pragma unroll
@@ -238,35 +319,86 @@ __global__ __launch_bounds__(256) void rel_fused_bwd_kernel(const float *__restr
   // ---- the next tile's inputs travel while the current one is worked on -------------------------------------------------
   f32x4 hp[TI];
   float pp[2], dq[3];
+  int sc = 0, NIs = SEL ? clampi(cnt[2], NI) : NI, NJs = SEL ? clampi(cnt[3], NJ) : NJ;   // SEL: the scene of unit u,
+  long sbeg = 0;                                                                           //   its first unit
   for (long u = u_beg; u < u_end;) {
   // ---- one key block (8 key columns of one scene): the stretch of its query blocks that falls into this workgroup's range --
-  const int grp = (int)(u / NI), ib0 = (int)(u - (long)grp * NI), ibe = (int)min((long)NI, ib0 + (u_end - u));
-  const int b = grp / NJ, j0 = (grp - b * NJ) * TJ, ibeg = ib0 * TI, iend = ibe * TI;
+  int b, j0, ib0, ibe;
+  long kstart;   // the key block's first unit
+  if (SEL && !dense) {
+    while (sc + 1 < B && u >= sbeg + (long)NIs * NJs) {   // (scenes with nothing selected hold no units)
+      sbeg += (long)NIs * NJs;
+      ++sc;
+      NIs = clampi(cnt[4 * sc + 2], NI), NJs = clampi(cnt[4 * sc + 3], NJ);
+    }
+    const long v = u - sbeg;
+    const int jb = (int)(v / NIs);
+    ib0 = (int)(v - (long)jb * NIs), ibe = (int)min((long)NIs, ib0 + (u_end - u));
+    b = sc, j0 = jb * TJ, kstart = sbeg + (long)jb * NIs;
+  } else {
+    const int grp = (int)(u / NI);
+    ib0 = (int)(u - (long)grp * NI), ibe = (int)min((long)NI, ib0 + (u_end - u));
+    b = grp / NJ, j0 = (grp - b * NJ) * TJ, kstart = (long)grp * NI;
+  }
   u += ibe - ib0;
+  // SEL in place: only the tiles whose query block and key block hold an active proposal
+  const int *rfl = SEL ? blk + (size_t)b * BS + 2 : nullptr;
+  auto next_tile = [&](int ib) -> int {
+    if (SEL && dense)
+      while (ib < ibe && !rfl[ib]) ++ib;
+    return ib;
+  };
+  if (SEL && dense && !rfl[NI + (j0 >> 3)]) continue;
+  int ib = next_tile(ib0);
+  if (ib >= ibe) continue;   // (dU of an unvisited stretch: the scan kernel's zeros)
+  int ibn = next_tile(ib + 1), ibn2 = ibn < ibe ? next_tile(ibn + 1) : ibe;
+  // SEL: i0, j0 count list entries; rows_of / KJ give the proposal behind an entry (clamped: no address leaves the scene)
+  const int *ql = SEL ? ws + sel_qi_off(B, K) + (size_t)b * K : nullptr, *kl = SEL ? ws + sel_kj_off(B, K) + (size_t)b * K : nullptr;
+  auto KJ = [&](int x) -> int { return SEL && !dense ? clampi(kl[j0 + x], K - 1) : j0 + x; };
+  const int kP = KJ(tid & 7), kH = KJ(jj), kU[2] = {KJ(2 * w), KJ(2 * w + 1)}, kR = KJ(2 * w + (l15 >> 3)), kZ = KJ(2 * w + (lg >> 1));
+  int kD[3], iD[3], oD[3];   // the thread's three dpred elements of a tile: key column, query entry, output
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    const int idx = tid + 256 * e, ii = idx / (TJ * NO), off = idx - ii * (TJ * NO), j = off / NO;
+    iD[e] = ii, oD[e] = off - j * NO, kD[e] = idx < TR * NO ? KJ(j) : 0;
+  }
   float uA[8][4];
   f32x4 uP[8], du[8];
 #pragma unroll
   for (int n = 0; n < 8; ++n) {
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) uA[n][ks] = U[(((size_t)b * K + j0 + 2 * w + (ks >> 1)) * H + 4 * (ks & 1) + lg) * C + 16 * n + l15];
+    for (int ks = 0; ks < 4; ++ks) uA[n][ks] = U[(((size_t)b * K + kU[ks >> 1]) * H + 4 * (ks & 1) + lg) * C + 16 * n + l15];
     // dP: row (key column l15 >> 3, head l15 & 7) of U, contraction over the channels
-    uP[n] = ld4(U + (((size_t)b * K + j0 + 2 * w + (l15 >> 3)) * H + (l15 & 7)) * C + 16 * n + 4 * lg);
+    uP[n] = ld4(U + (((size_t)b * K + kR) * H + (l15 & 7)) * C + 16 * n + 4 * lg);
     du[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  auto request = [&](int i0) {
-    p_tile_request(P, b, K, i0, j0, pp);
+  // SEL: the proposals behind the 8 query entries of a tile, entry (lane & 7) in every lane: read from the list one tile before
+  // the loads that use them are issued, so that no load waits for an index; a lane fetches its rows from its wave's lanes 0 .. 7
+  int ha = 0, hb = 0;   // the tile in flight, the tile after it
+  auto rows_of = [&](int i0) -> int { return !SEL ? 0 : dense ? i0 + (lane & 7) : clampi(ql[i0 + (lane & 7)], K - 1); };
+  auto row = [&](int i0, int h, int x) -> int { return SEL ? __shfl(h, x & 7) : i0 + x; };
+  auto request = [&](int i0, int h) {
+    p_tile_request_at(P, b, K, row(i0, h, (tid >> 3) & 7), kP, pp);
+    int rD[3];
 #pragma unroll
-    for (int e = 0; e < 3; ++e) {   // dpred rows of the tile: 8 runs (one per query) of 72 contiguous floats
-      const int idx = tid + 256 * e, ii = idx / (TJ * NO), off = idx - ii * (TJ * NO);
-      dq[e] = idx < TR * NO ? dpred[(((size_t)b * K + i0 + ii) * K + j0) * NO + off] : 0.f;
+    for (int e = 0; e < 3; ++e) rD[e] = row(i0, h, iD[e]);
+#pragma unroll
+    for (int e = 0; e < 3; ++e)   // dpred rows of the tile: 8 runs (one per query) of 72 contiguous floats
+      dq[e] = tid + 256 * e < TR * NO ? dpred[(((size_t)b * K + rD[e]) * K + kD[e]) * NO + oD[e]] : 0.f;
+#pragma unroll
+    for (int ii = 0; ii < TI; ++ii) {
+      const int r = SEL ? __builtin_amdgcn_readlane(h, ii) : i0 + ii;
+      hp[ii] = ld4(hid2 + (((size_t)b * K + r) * K + kH) * C + 4 * c4);
     }
-#pragma unroll
-    for (int ii = 0; ii < TI; ++ii) hp[ii] = ld4(hid2 + pair_row(b, K, i0, j0, jj * TI + ii) * C + 4 * c4);
   };
-  request(ibeg);
+  ha = rows_of(ib * TI);
+  if (ibn < ibe) hb = rows_of(ibn * TI);
+  request(ib * TI, ha);
 
-  for (int i0 = ibeg; i0 < iend; i0 += TI) {
+  for (; ib < ibe; ib = ibn, ibn = ibn2, ibn2 = ibn < ibe ? next_tile(ibn + 1) : ibe) {
+    const int i0 = ib * TI;
     __syncthreads();   // the previous tile's readers of every LDS buffer are done
+    const int qR = row(i0, ha, l15 & 7);   // the query row of this lane's dP results
     p_tile_store(pp, s_p);
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
@@ -275,7 +407,11 @@ __global__ __launch_bounds__(256) void rel_fused_bwd_kernel(const float *__restr
     }
 #pragma unroll
     for (int ii = 0; ii < TI; ++ii) st4(&s_x[(jj * TI + ii) * LDT + 4 * c4], hp[ii]);
-    if (i0 + TI < iend) request(i0 + TI);
+    if (ibn < ibe) {
+      ha = hb;
+      request(ibn * TI, ha);
+      if (ibn2 < ibe) hb = rows_of(ibn2 * TI);
+    }
     __syncthreads();
     float dB[3];   // dpred of row 16 w + l15, three k steps of 4 outputs (either operand side: same lane structure)
 #pragma unroll
@@ -371,7 +507,7 @@ __global__ __launch_bounds__(256) void rel_fused_bwd_kernel(const float *__restr
       }
       acc += accb;
       if ((lg >> 1) == (l15 >> 3)) {
-        float *o = dP + (((size_t)b * H + 4 * (lg & 1)) * K + i0 + (l15 & 7)) * K + j0 + 2 * w + (l15 >> 3);
+        float *o = dP + (((size_t)b * H + 4 * (lg & 1)) * K + qR) * K + kR;
 #pragma unroll
         for (int uu = 0; uu < 4; ++uu) o[(size_t)uu * K * K] = acc[uu];
       }
@@ -389,15 +525,17 @@ __global__ __launch_bounds__(256) void rel_fused_bwd_kernel(const float *__restr
   }
   {   // this stretch's share of dU: du[n][uu] = dU[key column 2 w + (lg >> 1), head 4 (lg & 1) + uu, channel 16 n + l15].
       // Slot = position of this workgroup among those that share the key block; the one that ends it clears the unused slots.
-    const long first = ((long)grp * NI + 1) * gridDim.x;
-    const int slot = (int)(blockIdx.x - ((first + NU - 1) / NU - 1));
+    const long first = (kstart + 1) * gridDim.x;
+    const int slot = (int)(blockIdx.x - (SEL && !dense ? kstart / L : (first + NU - 1) / NU - 1));
     const size_t slab = (size_t)B * K * H * C;
-    float *duo = dU + (size_t)slot * slab + (((size_t)b * K + j0 + 2 * w + (lg >> 1)) * H + 4 * (lg & 1)) * C + l15;
+    float *duo = dU + (size_t)slot * slab + (((size_t)b * K + kZ) * H + 4 * (lg & 1)) * C + l15;
+    if (!SEL || slot < Z) {   // (SEL: the host sized Z by the rule of the partition; the test keeps a store inside dU regardless)
 #pragma unroll
-    for (int n = 0; n < 8; ++n)
+      for (int n = 0; n < 8; ++n)
 #pragma unroll
-      for (int uu = 0; uu < 4; ++uu) duo[uu * C + 16 * n] = du[n][uu];
-    if (ibe == NI)
+        for (int uu = 0; uu < 4; ++uu) duo[uu * C + 16 * n] = du[n][uu];
+    }
+    if (!SEL && ibe == NI)
       for (int z = slot + 1; z < Z; ++z)
 #pragma unroll
         for (int n = 0; n < 8; ++n)
@@ -432,6 +570,126 @@ __global__ __launch_bounds__(256) void rel_fused_bwd_kernel(const float *__restr
 #pragma unroll
     for (int g = 0; g < 16; ++g) a += s_sum[g * C + tid];
     pb1[tid] = a;
+  }
+}
+
+__global__ __launch_bounds__(256) void rel_fused_bwd_kernel(const float *__restrict__ dpred, const float *__restrict__ hid2,
+                                                            const float *__restrict__ P, const float *__restrict__ U,
+                                                            const float *__restrict__ b1, const float *__restrict__ W2,
+                                                            const float *__restrict__ W3, int B, int K, int Z,
+                                                            float *__restrict__ dP, float *__restrict__ dU, float *__restrict__ part) {
+  rel_bwd_body<false>(dpred, hid2, P, U, b1, W2, W3, B, K, Z, nullptr, dP, dU, part);
+}
+__global__ __launch_bounds__(256) void rel_fused_bwd_sel_kernel(const float *__restrict__ dpred, const float *__restrict__ hid2,
+                                                                const float *__restrict__ P, const float *__restrict__ U,
+                                                                const float *__restrict__ b1, const float *__restrict__ W2,
+                                                                const float *__restrict__ W3, int B, int K, int Z,
+                                                                const int *__restrict__ ws, float *__restrict__ dP,
+                                                                float *__restrict__ dU, float *__restrict__ part) {
+  rel_bwd_body<true>(dpred, hid2, P, U, b1, W2, W3, B, K, Z, ws, dP, dU, part);
+}
+
+// ---- which query rows and key columns of dpred carry a gradient ----------------------------------------------------------
+// One workgroup per query row (b, i): its K x 9 values of dpred, read once.  Row flag = any value != 0 (-0 is not, NaN is);
+// the row's key columns leave as a bit mask, OR-ed over the scene's rows by the compaction below.  Every word has one writer:
+// no atomics, nothing to clear.  The same workgroup writes the zeros of its share of the outputs: dP[b, :, i, :] and
+// dU[:, b, i, :, :] -- what the backward kernel does not visit stays zero.
+__global__ __launch_bounds__(256) void rel_sel_scan_kernel(const float *__restrict__ dpred, int B, int K, int Z, int *__restrict__ ws,
+                                                           float *__restrict__ dP, float *__restrict__ dU) {
+  __shared__ int s_f[256];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, NW = sel_nw(K);
+  const size_t row = blockIdx.x;
+  const int b = (int)(row / K), i = (int)(row - (size_t)b * K);
+  unsigned long long *colbits = reinterpret_cast<unsigned long long *>(ws + sel_colbits_off(B, K)) + row * NW;
+  bool any = false;
+  for (int c0 = 0; c0 < K; c0 += 256) {   // 256 key columns = 2304 contiguous floats at a time
+    const int nq = min(256, K - c0) * NO / 4;
+    s_f[tid] = 0;
+    __syncthreads();
+    const float *d = dpred + (row * K + c0) * NO;
+    for (int q = tid; q < nq; q += 256) {
+      const f32x4 v = ld4(d + 4 * q);
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (v[c] != 0.f) s_f[(4 * q + c) / NO] = 1, any = true;   // (every writer stores the same value)
+    }
+    __syncthreads();
+    const unsigned long long bal = __ballot(s_f[tid] != 0);
+    if (lane == 0 && (c0 >> 6) + w < NW) colbits[(c0 >> 6) + w] = bal;
+    __syncthreads();
+  }
+  const int r = __syncthreads_or(any);
+  if (tid == 0) ws[sel_rowflag_off(B, K) + row] = r != 0;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  for (int h = 0; h < H; ++h) {
+    float *o = dP + (((size_t)b * H + h) * K + i) * K;
+    for (int q = tid; q < K / 4; q += 256) st4(o + 4 * q, zero);
+  }
+  for (int z = 0; z < Z; ++z) {
+    float *o = dU + ((size_t)z * B * K + row) * H * C;
+    for (int q = tid; q < H * C / 4; q += 256) st4(o + 4 * q, zero);
+  }
+}
+
+// flag[0 .. K) -> list: the flagged indices ascending, then (up to the next multiple of 8) the first unflagged ones ascending
+__device__ __forceinline__ int compact_list(const int *flag, int K, int *list, int *s_wc) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int n = 0;
+  for (int c0 = 0; c0 < K; c0 += 256) n += __syncthreads_count(c0 + tid < K && flag[c0 + tid] != 0);
+  const int pad = ((n + 7) & ~7) - n;
+  int base = 0;
+  for (int c0 = 0; c0 < K; c0 += 256) {
+    const int j = c0 + tid;
+    const bool f = j < K && flag[j] != 0;
+    const unsigned long long bal = __ballot(f);
+    if (lane == 0) s_wc[w] = __popcll(bal);
+    __syncthreads();
+    int a = base + __popcll(bal & ((1ull << lane) - 1));   // flagged indices below j
+    for (int ww = 0; ww < w; ++ww) a += s_wc[ww];
+    if (f) list[a] = j;
+    else if (j < K && j - a < pad) list[n + j - a] = j;
+    base += (s_wc[0] + s_wc[1]) + (s_wc[2] + s_wc[3]);
+    __syncthreads();
+  }
+  return n;
+}
+
+// One workgroup per scene: key-column flags from the rows' bit masks, both lists, the counts.
+__global__ __launch_bounds__(256) void rel_sel_compact_kernel(int B, int K, int *__restrict__ ws) {
+  __shared__ int s_wc[4];
+  const int tid = threadIdx.x, b = blockIdx.x, NW = sel_nw(K);
+  const unsigned long long *colbits = reinterpret_cast<const unsigned long long *>(ws + sel_colbits_off(B, K)) + (size_t)b * K * NW;
+  int *colflag = ws + sel_colflag_off(B, K) + (size_t)b * K;
+  for (int j = tid; j < K; j += 256) {
+    unsigned long long acc = 0;
+#pragma unroll 8
+    for (int i = 0; i < K; ++i) acc |= colbits[(size_t)i * NW + (j >> 6)];
+    colflag[j] = (int)((acc >> (j & 63)) & 1);
+  }
+  __threadfence_block();
+  __syncthreads();
+  const int nq = compact_list(ws + sel_rowflag_off(B, K) + (size_t)b * K, K, ws + sel_qi_off(B, K) + (size_t)b * K, s_wc);
+  const int nk = compact_list(colflag, K, ws + sel_kj_off(B, K) + (size_t)b * K, s_wc);
+  // (colflag: written above by other threads of this workgroup; compact_list's barriers lie in between)
+  const int *rowflag = ws + sel_rowflag_off(B, K) + (size_t)b * K;
+  int *bl = ws + sel_blk_off(B, K) + (size_t)b * sel_blk_stride(K);
+  const int NB = K / 8;
+  int rbn = 0, cbn = 0;
+  for (int c0 = 0; c0 < NB; c0 += 256) {
+    const int ib = c0 + tid;
+    int rf = 0, cf = 0;
+    if (ib < NB) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) rf |= rowflag[8 * ib + k], cf |= colflag[8 * ib + k];
+      bl[2 + ib] = rf != 0, bl[2 + NB + ib] = cf != 0;
+    }
+    rbn += __syncthreads_count(rf != 0);
+    cbn += __syncthreads_count(cf != 0);
+  }
+  if (tid == 0) {
+    int *cnt = ws + sel_cnt_off(B, K) + 4 * b;
+    cnt[0] = nq, cnt[1] = nk, cnt[2] = (nq + 7) >> 3, cnt[3] = (nk + 7) >> 3;
+    bl[0] = rbn, bl[1] = cbn;
   }
 }
 
@@ -477,6 +735,13 @@ extern "C" int spacap_relation_fused_supported(int H_, int K, int C_, int NO_) {
 extern "C" int spacap_relation_fused_nparts(int B, int K) { return B > 0 && K >= 8 ? grid_size(B, K, 1) : 0; }
 extern "C" int spacap_relation_fused_zsplit(int B, int K, int nparts) { return B > 0 && K >= 8 && nparts > 0 ? du_slots(B, K, nparts) : 0; }
 extern "C" int spacap_relation_fused_part_floats(void) { return PART; }
+// the selected backward's ranges are at least ceil(NI_max / (zslots - 1)) units long: three slots keep them within twice the even share
+extern "C" int spacap_relation_fused_sel_zsplit(int B, int K, int nparts) {
+  return B > 0 && K >= 8 && nparts > 0 ? std::max(3, du_slots(B, K, nparts)) : 0;
+}
+extern "C" size_t spacap_relation_fused_sel_workspace_bytes(int B, int K) {
+  return B > 0 && K >= 8 ? (sel_blk_off(B, K) + (size_t)B * sel_blk_stride(K)) * sizeof(int) : 0;
+}
 
 extern "C" int spacap_relation_fused_fwd_f32(const float *P, const float *U, const float *b1, const float *W2, const float *b2,
                                              const float *W3, const float *b3, int B, int K, float *hid2, float *pred,
@@ -507,6 +772,43 @@ extern "C" int spacap_relation_fused_bwd_f32(const float *dpred, const float *hi
                  "%s: (nparts=%d, zslots=%d) do not fit (B=%d, K=%d)", what, nparts, zslots, B, K);
   hipLaunchKernelGGL(rel_fused_bwd_kernel, dim3(nparts), dim3(256), BWD_LDS, spacap::as_stream(stream), dpred, hid2, P, U, b1, W2, W3, B, K,
                      zslots, dP, dU, part);
+  SPACAP_CHECK_LAUNCH(what);
+  return SPACAP_OK;
+}
+
+static int rel_sel_lists(const char *what, const float *dpred, int B, int K, int zslots, float *dP, float *dU, void *workspace,
+                         spacap_stream_t stream) {
+  SPACAP_REQUIRE(B >= 0 && K >= 8 && K % 8 == 0 && B <= 65535 && zslots >= 1, "%s: (B=%d, K=%d, zslots=%d) unsupported", what, B, K, zslots);
+  if (B == 0) return SPACAP_OK;
+  SPACAP_REQUIRE(dpred && dP && dU && workspace, "%s: null pointer", what);
+  SPACAP_REQUIRE(((uintptr_t)dpred | (uintptr_t)dP | (uintptr_t)dU) % 16 == 0 && (uintptr_t)workspace % 8 == 0, "%s: unaligned buffer", what);
+  hipLaunchKernelGGL(rel_sel_scan_kernel, dim3((unsigned)B * K), dim3(256), 0, spacap::as_stream(stream), dpred, B, K, zslots,
+                     static_cast<int *>(workspace), dP, dU);
+  SPACAP_CHECK_LAUNCH(what);
+  hipLaunchKernelGGL(rel_sel_compact_kernel, dim3(B), dim3(256), 0, spacap::as_stream(stream), B, K, static_cast<int *>(workspace));
+  SPACAP_CHECK_LAUNCH(what);
+  return SPACAP_OK;
+}
+
+extern "C" int spacap_relation_fused_sel_lists_f32(const float *dpred, int B, int K, int zslots, float *dP, float *dU, void *workspace,
+                                                   spacap_stream_t stream) {
+  return rel_sel_lists("spacap_relation_fused_sel_lists_f32", dpred, B, K, zslots, dP, dU, workspace, stream);
+}
+
+extern "C" int spacap_relation_fused_bwd_sel_f32(const float *dpred, const float *hid2, const float *P, const float *U, const float *b1,
+                                                 const float *W2, const float *W3, int B, int K, int nparts, int zslots, float *dP,
+                                                 float *dU, float *part, void *workspace, spacap_stream_t stream) {
+  const char *what = "spacap_relation_fused_bwd_sel_f32";
+  SPACAP_REQUIRE(B >= 0 && K >= 8 && K % 8 == 0 && B <= 65535, "%s: (B=%d, K=%d) unsupported", what, B, K);
+  if (B == 0) return SPACAP_OK;
+  SPACAP_REQUIRE(dpred && hid2 && P && U && b1 && W2 && W3 && dP && dU && part && workspace, "%s: null pointer", what);
+  static unsigned long long lds_ok = 0;
+  SPACAP_CHECK_HIP(spacap::allow_dynamic_lds(reinterpret_cast<const void *>(&rel_fused_bwd_sel_kernel), (int)BWD_LDS, lds_ok), what);
+  SPACAP_REQUIRE(nparts >= 1 && nparts <= B * (K / TJ) * (K / TI) && zslots >= std::max(3, du_slots(B, K, nparts)),
+                 "%s: (nparts=%d, zslots=%d) do not fit (B=%d, K=%d)", what, nparts, zslots, B, K);
+  if (const int rc = rel_sel_lists(what, dpred, B, K, zslots, dP, dU, workspace, stream)) return rc;
+  hipLaunchKernelGGL(rel_fused_bwd_sel_kernel, dim3(nparts), dim3(256), BWD_LDS, spacap::as_stream(stream), dpred, hid2, P, U, b1, W2, W3,
+                     B, K, zslots, static_cast<const int *>(workspace), dP, dU, part);
   SPACAP_CHECK_LAUNCH(what);
   return SPACAP_OK;
 }

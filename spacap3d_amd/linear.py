@@ -394,7 +394,9 @@ class RelationHead(Function):
     (csrc/relation_fused.hip): pred = W3 relu(W2 relu(b1 + sum_h P U) + b2) + b3 on the B*K*K pairs, with
     U[b,j,h,:] = V[b,h,j,:] W1[:, 16h:16h+16]^T formed by the caller.  Neither the pair feature nor the first hidden layer
     nor any gradient of pair size exists in HBM: the forward stores hid2 (the backward's one large input) and pred; the
-    backward returns dP, the dU partials and per-workgroup partial sums of dW2, dW3, db1, db2, db3."""
+    backward returns dP, the dU partials and per-workgroup partial sums of dW2, dW3, db1, db2, db3.  It visits only the
+    (query row) x (key column) sub-grid on which the incoming gradient is not zero (found on the device from the gradient
+    itself: the relation loss weights pair (i, j) by "both proposals selected")."""
 
     @staticmethod
     def forward(ctx, P, U, b1, W2, b2, W3, b3):
@@ -419,14 +421,16 @@ class RelationHead(Function):
         with torch.cuda.device(dev):
             PW = int(lib.spacap_relation_fused_part_floats())
             nparts = int(lib.spacap_relation_fused_nparts(B, K))
-            zslots = int(lib.spacap_relation_fused_zsplit(B, K, nparts))
+            zslots = int(lib.spacap_relation_fused_sel_zsplit(B, K, nparts))
             part = torch.empty(nparts, PW, dtype=torch.float32, device=dev)
             dP = torch.empty_like(P)
             dU = torch.empty(zslots, *U.shape, dtype=torch.float32, device=dev)
-            check(lib.spacap_relation_fused_bwd_f32(g.data_ptr(), hid2.data_ptr(), P.data_ptr(), U.data_ptr(), b1.data_ptr(),
-                                                    W2.data_ptr(), W3.data_ptr(), B, K, nparts, zslots, dP.data_ptr(), dU.data_ptr(),
-                                                    part.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                  "spacap_relation_fused_bwd_f32")
+            ws = torch.empty(int(lib.spacap_relation_fused_sel_workspace_bytes(B, K)), dtype=torch.uint8, device=dev)
+            check(lib.spacap_relation_fused_bwd_sel_f32(g.data_ptr(), hid2.data_ptr(), P.data_ptr(), U.data_ptr(), b1.data_ptr(),
+                                                        W2.data_ptr(), W3.data_ptr(), B, K, nparts, zslots, dP.data_ptr(),
+                                                        dU.data_ptr(), part.data_ptr(), ws.data_ptr(),
+                                                        torch.cuda.current_stream(dev).cuda_stream),
+                  "spacap_relation_fused_bwd_sel_f32")
             s = sum_slabs(part, deferrable=True)
         o = 128 * 128
         dW2, dW3 = s[:o].view(128, 128), s[o:o + 9 * 128].view(9, 128)
