@@ -186,7 +186,9 @@ int spacap_mha_fwd_f32(const float *q, const float *k, const float *v, long q_sb
  * bytes of scratch.  Outputs dq f32 [B,Lq,h,d_k], dk,dv f32 [B,Lk,h,d_k] (the layout of the projections
  * before `.transpose(1,2)`); every element is written.  grad_row_stride: floats between consecutive rows
  * (b, position) of dq / dk / dv; 0 = dense (h*d_k).  A packed q|k|v projection (one GEMM) passes 3*h*d_k and
- * three pointers into one [B,L,3*h*d_k] buffer. */
+ * three pointers into one [B,L,3*h*d_k] buffer.  No alignment is asked of q, k, v or d_out beyond that of a float:
+ * 16-byte loads are used where a base and its strides allow them, with the same values either way.  Lq == 0 (no
+ * query, dense gradients only): dk and dv are zero-filled, dq is empty, and stats, d_out, workspace may be NULL. */
 size_t spacap_mha_bwd_workspace_bytes(int B, int h, int Lq);
 int spacap_mha_bwd_f32(const float *q, const float *k, const float *v, long q_sb, long q_sh,
                        long q_sl, long k_sb, long k_sh, long k_sl, long v_sb, long v_sh, long v_sl,
@@ -198,7 +200,9 @@ int spacap_mha_bwd_f32(const float *q, const float *k, const float *v, long q_sb
 
 /* As spacap_mha_bwd_f32 with delta f32 [B,h,Lq] = sum_k p_attn d(p_attn) precomputed by the caller (without a gradient on
  * p_attn itself: sum_d out[b,q,head,d] d_out[b,q,head,d]; spacap_tf_rows_f32 emits it): the dQ and dK / dV halves are then
- * independent and run as ONE launch.  Self-attention shapes only (Lq, Lk both <= 64 or both > 64). */
+ * independent and run as ONE launch.  Self-attention shapes only (Lq, Lk both <= 64 or both > 64); any other pair is
+ * refused and nothing is written.  Lq == 0 is taken as by spacap_mha_bwd_f32: dk and dv (dense) are zero-filled, so that
+ * here too every element of the outputs is written, and stats, d_out, delta may be NULL. */
 int spacap_mha_bwd_delta_f32(const float *q, const float *k, const float *v, long q_sb, long q_sh,
                              long q_sl, long k_sb, long k_sh, long k_sl, long v_sb, long v_sh, long v_sl,
                              const uint8_t *mask, long mask_sb, long mask_sq, const float *bias,

@@ -233,6 +233,8 @@ def attention(query, key, value, mask=None, dropout_p=0.0, training=False, need_
     """(out (B,h,Lq,d_k), p_attn (B,h,Lq,Lk) or None); see the module docstring."""
     B, h, Lq, dk = query.shape
     Lk = key.shape[2]
+    if bias is not None and bias.requires_grad:
+        raise RuntimeError("attention: no gradient is formed for the bias (it is a constant of the logits); pass bias.detach()")
     m, msb, msq = _prep_mask(mask, B, Lq, Lk)
     p = float(dropout_p) if training else 0.0
     seed = _next_seed() if p > 0.0 else 0

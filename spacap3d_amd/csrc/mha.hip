@@ -51,6 +51,7 @@ struct MhaArgs {
   float *dq, *dk, *dv, *delta;      // backward outputs / scratch
   long g_sl;                        // row stride (floats) of dq / dk / dv: h * d_k when dense
   int vec;                          // q / k / v rows are 16-byte aligned (bases and strides): operands by 16-byte loads
+  int dvec;                         // the same for the rows of d_out (dense: its base decides)
 };
 
 // Dropout keep decision of element (b, head, q, key): the counter hash of dropout.hpp over the flat index into p, the
@@ -572,7 +573,7 @@ __device__ __forceinline__ void bwd_dq_split_body(const MhaArgs &A, int bx) {
 #pragma unroll
   for (int j = 0; j < DK / 16; ++j) {
     qv[j] = ldv(qp + 16 * j + 4 * lg, A.vec);
-    dov[j] = ldv(dop + 16 * j + 4 * lg, (DK * A.h) % 4 == 0);
+    dov[j] = ldv(dop + 16 * j + 4 * lg, A.dvec);
   }
   const float *st = A.stats + (((size_t)b * A.h + hh) * A.Lq + qc) * 2;
   const float m = st[0], inv_l = 1.0f / st[1];
@@ -702,7 +703,7 @@ __device__ __forceinline__ void bwd_dkv_split_body(const MhaArgs &A, int bx) {
     f32x4 s4 = {0.f, 0.f, 0.f, 0.f}, g4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < DK / 16; ++j) {
-      const f32x4 qq = ldv(qp + 16 * j + 4 * lg, A.vec), dd = ldv(dop + 16 * j + 4 * lg, (DK * A.h) % 4 == 0);
+      const f32x4 qq = ldv(qp + 16 * j + 4 * lg, A.vec), dd = ldv(dop + 16 * j + 4 * lg, A.dvec);
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         s4 = MFMA16(qq[s], kv[j][s], s4);
@@ -800,6 +801,7 @@ int fill_args(MhaArgs &A, const char *what, const float *q, const float *k, cons
     return aligned16(p) && a % 4 == 0 && b2 % 4 == 0 && c % 4 == 0;
   };
   A.vec = al(q, q_sb, q_sh, q_sl) && al(k, k_sb, k_sh, k_sl) && al(v, v_sb, v_sh, v_sl) ? 1 : 0;
+  A.dvec = 0;
   A.out = A.p_out = A.stats = nullptr;
   A.d_out = A.d_p = nullptr;
   A.dq = A.dk = A.dv = A.delta = nullptr;
@@ -901,6 +903,7 @@ extern "C" int spacap_mha_bwd_f32(const float *q, const float *k, const float *v
   SPACAP_REQUIRE(stats && d_out && workspace, "spacap_mha_bwd_f32: null input");
   A.stats = const_cast<float *>(stats);
   A.d_out = d_out; A.d_p = d_p;
+  A.dvec = aligned16(d_out) ? 1 : 0;
   A.dq = dq; A.dk = dk; A.dv = dv;
   A.delta = reinterpret_cast<float *>(workspace);
   if (d_k == 16) launch_bwd<16>(A, s);
@@ -925,13 +928,21 @@ extern "C" int spacap_mha_bwd_delta_f32(const float *q, const float *k, const fl
   int rc = fill_args(A, what, q, k, v, q_sb, q_sh, q_sl, k_sb, k_sh, k_sl, v_sb, v_sh, v_sl, mask,
                      mask_sb, mask_sq, bias, bias_sb, bias_sh, bias_sq, B, h, Lq, Lk, d_k, scale, dropout_p, seed, seed_dev);
   if (rc) return rc;
-  if (B == 0 || Lq == 0) return SPACAP_OK;
-  SPACAP_REQUIRE(dq && dk && dv && stats && d_out && delta, "%s: null pointer", what);
+  if (B == 0) return SPACAP_OK;
+  SPACAP_REQUIRE(dq && dk && dv, "%s: null output", what);
   SPACAP_REQUIRE(grad_row_stride == 0 || grad_row_stride >= (long)h * d_k, "%s: bad grad_row_stride", what);
   hipStream_t s = spacap::as_stream(stream);
   A.g_sl = grad_row_stride ? grad_row_stride : (long)h * d_k;
+  if (Lq == 0) {   // no query, no gradient: as spacap_mha_bwd_f32
+    SPACAP_REQUIRE(A.g_sl == (long)h * d_k, "%s: Lq == 0 needs dense gradients", what);
+    SPACAP_CHECK_HIP(hipMemsetAsync(dk, 0, sizeof(float) * (size_t)B * Lk * h * d_k, s), what);
+    SPACAP_CHECK_HIP(hipMemsetAsync(dv, 0, sizeof(float) * (size_t)B * Lk * h * d_k, s), what);
+    return SPACAP_OK;
+  }
+  SPACAP_REQUIRE(stats && d_out && delta, "%s: null input", what);
   A.stats = const_cast<float *>(stats);
   A.d_out = d_out; A.d_p = nullptr;
+  A.dvec = aligned16(d_out) ? 1 : 0;
   A.dq = dq; A.dk = dk; A.dv = dv;
   A.delta = const_cast<float *>(delta);
   const bool ok = d_k == 16 ? launch_bwd_both<16>(A, s) : d_k == 32 ? launch_bwd_both<32>(A, s) : launch_bwd_both<64>(A, s);

@@ -48,6 +48,13 @@ def test_argument_validation_needs_no_device():
     assert lib.spacap_mha_fwd_f32(None, None, None, *z, None, 0, 0, None, 0, 0, 0, 1, 8, 16, 16, 24, 0.25, 0.0, 0, None,
                                   None, None, None, None) == -1
     assert b"d_k=24" in lib.spacap_last_error()
+    # Lq == 0 through both attention backward entry points: the outputs are asked for, and dense, before anything runs
+    fake = 1 << 12   # non-null and never dereferenced: every call below returns from its argument checks
+    head = (fake, fake, fake, *z, None, 0, 0, None, 0, 0, 0, 2, 3, 0, 33, 16, 0.25, 0.0, 0, None)
+    for entry, inputs in (("spacap_mha_bwd_f32", (None,) * 4), ("spacap_mha_bwd_delta_f32", (None,) * 3)):
+        f = getattr(lib, entry)
+        assert f(*head, *inputs, None, None, None, 0, None) == -1 and b"null output" in lib.spacap_last_error()
+        assert f(*head, *inputs, fake, fake, fake, 3 * 48, None) == -1 and b"dense" in lib.spacap_last_error()
 
 
 def test_fps_workspace_covers_the_dispatched_bucket_template():
