@@ -87,6 +87,19 @@ def _next_seed():
     return _CALL_COUNTER[0]
 
 
+def mha_args(q_ptr, k_ptr, v_ptr, q_strides, k_strides, v_strides, mask_u8, mask_sb, mask_sq, bias, B, h, Lq, Lk, dk, scale,
+             dropout_p, seed, device):
+    """The leading arguments spacap_mha_fwd_f32, spacap_mha_bwd_f32 and spacap_mha_bwd_delta_f32 share: the three operand
+    pointers and their (scene, head, row) strides, mask, bias, sizes, scale, and the dropout triple (probability, host seed,
+    the device's rng word -- passed only when something is dropped)."""
+    bs = (bias.stride(0), bias.stride(1), bias.stride(2)) if bias is not None else (0, 0, 0)
+    return (q_ptr, k_ptr, v_ptr, *q_strides, *k_strides, *v_strides,
+            mask_u8.data_ptr() if mask_u8 is not None else None, mask_sb, mask_sq,
+            bias.data_ptr() if bias is not None else None, *bs,
+            B, h, Lq, Lk, dk, scale, float(dropout_p), int(seed),
+            rng_state(device).data_ptr() if dropout_p > 0.0 else None)
+
+
 class FusedAttention(Function):
     @staticmethod
     def forward(ctx, q, k, v, mask_u8, mask_sb, mask_sq, bias, dropout_p, seed, need_p):
@@ -105,13 +118,9 @@ class FusedAttention(Function):
             out = torch.empty(B, Lq, h, dk, dtype=torch.float32, device=q.device)
             p = torch.empty(B, h, Lq, Lk, dtype=torch.float32, device=q.device) if need_p else None
             lse = torch.empty(B, h, Lq, 2, dtype=torch.float32, device=q.device)  # (row max, row sum)
-            bs = (bias.stride(0), bias.stride(1), bias.stride(2)) if bias is not None else (0, 0, 0)
             check(lib.spacap_mha_fwd_f32(
-                q.data_ptr(), k.data_ptr(), v.data_ptr(), *_strides3(q), *_strides3(k), *_strides3(v),
-                mask_u8.data_ptr() if mask_u8 is not None else None, mask_sb, mask_sq,
-                bias.data_ptr() if bias is not None else None, *bs,
-                B, h, Lq, Lk, dk, scale, float(dropout_p), int(seed),
-                rng_state(q.device).data_ptr() if dropout_p > 0.0 else None,
+                *mha_args(q.data_ptr(), k.data_ptr(), v.data_ptr(), _strides3(q), _strides3(k), _strides3(v), mask_u8, mask_sb,
+                          mask_sq, bias, B, h, Lq, Lk, dk, scale, dropout_p, seed, q.device),
                 out.data_ptr(), p.data_ptr() if need_p else None, lse.data_ptr(),
                 torch.cuda.current_stream(q.device).cuda_stream), "spacap_mha_fwd_f32")
         ctx.save_for_backward(q, k, v, mask_u8, bias, lse)
@@ -139,14 +148,10 @@ class FusedAttention(Function):
             dv = torch.empty(B, Lk, h, dk, dtype=torch.float32, device=q.device)
             ws = torch.empty(max(int(lib.spacap_mha_bwd_workspace_bytes(B, h, Lq)), 16), dtype=torch.uint8,
                              device=q.device)
-            bs = (bias.stride(0), bias.stride(1), bias.stride(2)) if bias is not None else (0, 0, 0)
             check(lib.spacap_mha_bwd_f32(
-                q.data_ptr(), k.data_ptr(), v.data_ptr(), *_strides3(q), *_strides3(k), *_strides3(v),
-                mask_u8.data_ptr() if mask_u8 is not None else None, mask_sb, mask_sq,
-                bias.data_ptr() if bias is not None else None, *bs,
-                B, h, Lq, Lk, dk, scale, float(dropout_p), int(seed),
-                rng_state(q.device).data_ptr() if dropout_p > 0.0 else None, lse.data_ptr(),
-                d_out_c.data_ptr(), d_p_c.data_ptr() if d_p_c is not None else None, ws.data_ptr(),
+                *mha_args(q.data_ptr(), k.data_ptr(), v.data_ptr(), _strides3(q), _strides3(k), _strides3(v), mask_u8, mask_sb,
+                          mask_sq, bias, B, h, Lq, Lk, dk, scale, dropout_p, seed, q.device),
+                lse.data_ptr(), d_out_c.data_ptr(), d_p_c.data_ptr() if d_p_c is not None else None, ws.data_ptr(),
                 dq.data_ptr(), dk_.data_ptr(), dv.data_ptr(), 0,
                 torch.cuda.current_stream(q.device).cuda_stream), "spacap_mha_bwd_f32")
         return (dq.transpose(1, 2), dk_.transpose(1, 2), dv.transpose(1, 2), None, None, None, None, None, None,
@@ -176,10 +181,8 @@ class FusedSelfAttentionPacked(Function):
             lse = torch.empty(B, h, L, 2, dtype=torch.float32, device=qkv.device)
             base = qkv.data_ptr()
             check(lib.spacap_mha_fwd_f32(
-                base, base + hd * es, base + 2 * hd * es, *strides, *strides, *strides,
-                mask_u8.data_ptr() if mask_u8 is not None else None, mask_sb, mask_sq, None, 0, 0, 0,
-                B, h, L, L, dk, scale, float(dropout_p), int(seed),
-                rng_state(qkv.device).data_ptr() if dropout_p > 0.0 else None,
+                *mha_args(base, base + hd * es, base + 2 * hd * es, strides, strides, strides, mask_u8, mask_sb, mask_sq, None,
+                          B, h, L, L, dk, scale, dropout_p, seed, qkv.device),
                 out.data_ptr(), p.data_ptr() if need_p else None, lse.data_ptr(),
                 torch.cuda.current_stream(qkv.device).cuda_stream), "spacap_mha_fwd_f32")
         ctx.save_for_backward(qkv, mask_u8, lse)
@@ -209,11 +212,9 @@ class FusedSelfAttentionPacked(Function):
                              device=qkv.device)
             base, gb = qkv.data_ptr(), dqkv.data_ptr()
             check(lib.spacap_mha_bwd_f32(
-                base, base + hd * es, base + 2 * hd * es, *strides, *strides, *strides,
-                mask_u8.data_ptr() if mask_u8 is not None else None, mask_sb, mask_sq, None, 0, 0, 0,
-                B, h, L, L, dk, scale, float(dropout_p), int(seed),
-                rng_state(qkv.device).data_ptr() if dropout_p > 0.0 else None, lse.data_ptr(),
-                d_out_c.data_ptr(), d_p_c.data_ptr() if d_p_c is not None else None, ws.data_ptr(),
+                *mha_args(base, base + hd * es, base + 2 * hd * es, strides, strides, strides, mask_u8, mask_sb, mask_sq, None,
+                          B, h, L, L, dk, scale, dropout_p, seed, qkv.device),
+                lse.data_ptr(), d_out_c.data_ptr(), d_p_c.data_ptr() if d_p_c is not None else None, ws.data_ptr(),
                 gb, gb + hd * es, gb + 2 * hd * es, three_hd,
                 torch.cuda.current_stream(qkv.device).cuda_stream), "spacap_mha_bwd_f32")
         return dqkv, None, None, None, None, None, None, None

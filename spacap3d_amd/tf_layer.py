@@ -257,7 +257,7 @@ class AttnFfn1(Function):
         if not qkv.is_cuda:
             raise RuntimeError("CPU not supported")
         import math
-        from .attention import rng_state
+        from .attention import mha_args
         qc, xr = qkv.contiguous(), xres.contiguous()
         B, L, three = qc.shape
         hd = three // 3
@@ -271,10 +271,9 @@ class AttnFfn1(Function):
         with torch.cuda.device(dev):
             a, lse = _new(dev, B, L, hd), _new(dev, B, heads, L, 2)
             base = qc.data_ptr()
-            check(lib.spacap_mha_fwd_f32(base, base + hd * es, base + 2 * hd * es, *strides, *strides, *strides, _p(mask_u8), mask_sb,
-                                         mask_sq, None, 0, 0, 0, B, heads, L, L, dk, scale, float(p_att), int(seed_att),
-                                         rng_state(dev).data_ptr() if p_att > 0.0 else None, a.data_ptr(), None, lse.data_ptr(), st),
-                  "spacap_mha_fwd_f32")
+            check(lib.spacap_mha_fwd_f32(*mha_args(base, base + hd * es, base + 2 * hd * es, strides, strides, strides, mask_u8,
+                                                   mask_sb, mask_sq, None, B, heads, L, L, dk, scale, p_att, seed_att, dev),
+                                         a.data_ptr(), None, lse.data_ptr(), st), "spacap_mha_fwd_f32")
             x1, n2, stats = _new(dev, *xr.shape), _new(dev, R, D_MODEL), _new(dev, R, 2)
             _rows(0, R, dev, a1=a, w1=Wo, bias1=bo, k1=D_MODEL, drop_p=p_sub, seed=seed1, res=xr, x_out=x1, ln_a=ln_a,
                   ln_b=ln_b, eps=eps, n_out=n2, stats=stats)
@@ -286,7 +285,7 @@ class AttnFfn1(Function):
 
     @staticmethod
     def backward(ctx, g_x1, g_hpre, g_parts):
-        from .attention import rng_state
+        from .attention import mha_args
         qc, mask_u8, lse, a, x1, n2, stats, ln_a, Wo, W1 = ctx.saved_tensors
         eps, p_sub, seed1, heads, mask_sb, mask_sq, p_att, seed_att, scale = ctx.meta
         B, L, three = qc.shape
@@ -320,11 +319,11 @@ class AttnFfn1(Function):
             dqkv = torch.empty_like(qc)
             base, gb = qc.data_ptr(), dqkv.data_ptr()
             # (the two halves of the attention gradient are independent once delta is known: one launch)
-            check(lib.spacap_mha_bwd_delta_f32(base, base + hd * es, base + 2 * hd * es, *strides, *strides, *strides, _p(mask_u8),
-                                               mask_sb, mask_sq, None, 0, 0, 0, B, heads, L, L, dk, scale, p_att, seed_att,
-                                               rng_state(dev).data_ptr() if p_att > 0.0 else None, lse.data_ptr(), da.data_ptr(),
-                                               delta.data_ptr(), gb, gb + hd * es, gb + 2 * hd * es, three, st),
-                  "spacap_mha_bwd_delta_f32")
+            check(lib.spacap_mha_bwd_delta_f32(*mha_args(base, base + hd * es, base + 2 * hd * es, strides, strides, strides,
+                                                         mask_u8, mask_sb, mask_sq, None, B, heads, L, L, dk, scale, p_att,
+                                                         seed_att, dev),
+                                               lse.data_ptr(), da.data_ptr(), delta.data_ptr(), gb, gb + hd * es,
+                                               gb + 2 * hd * es, three, st), "spacap_mha_bwd_delta_f32")
         return (dqkv, dx1, None, None, None, None, None, None, dWo, dbo, dln_a, dln_b, dW1, db1, None, None, None, None, None, None)
 
 

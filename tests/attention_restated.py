@@ -83,10 +83,10 @@ def tier(Lq, Lk, d_k):
     split = Lk > KEY_EDGES[1]                     # four waves share 16 queries and split the keys
     tiles = {1: 2, 2: 4, 3: 2, 4: 4, 5: 8}[t]     # 16-key tiles per wave
     four = Lq > QUERY_EDGE                        # four waves share 16 keys and split the queries
-    s = "_split" if split else ""
-    both = (f"mha_bwd_both{s}_kernel", tiles, d_k) if split == four else None
-    return Tier(t, (f"mha_fwd{s}_kernel", tiles, d_k), (f"mha_bwd_dq{s}_kernel", tiles, d_k),
-                ("mha_bwd_dkv_split_kernel" if four else "mha_bwd_dkv_kernel", d_k), both)
+    w = 4 if split else 1                         # template argument W: waves per 16-row tile
+    both = ("mha_bwd_both_kernel", tiles, d_k, w) if split == four else None
+    return Tier(t, ("mha_fwd_kernel", tiles, d_k, w), ("mha_bwd_dq_kernel", tiles, d_k, w),
+                ("mha_bwd_dkv_kernel", d_k, 4 if four else 1), both)
 
 
 # ---- the case tables ------------------------------------------------------------------------------------------------------

@@ -32,18 +32,18 @@ def test_float64_statement_reproduces_the_reference_outputs(tag):
 def test_tier_restates_the_dispatch_at_every_threshold():
     """Both sides of each key-count edge and of the query-count edge, against the instantiations written out by hand from
     launch_fwd, launch_bwd and launch_bwd_both."""
-    want = {1: ("", 2), 2: ("", 4), 3: ("_split", 2), 4: ("_split", 4), 5: ("_split", 8)}
+    want = {1: (1, 2), 2: (1, 4), 3: (4, 2), 4: (4, 4), 5: (4, 8)}   # tier: (W waves per 16-row tile, NT key tiles per wave)
     edges = [(1, 1), (32, 1), (33, 2), (64, 2), (65, 3), (128, 3), (129, 4), (256, 4), (257, 5), (512, 5)]
     for d in R.D_KS:
         for Lk, t in edges:
             for Lq in (1, 64, 65, 512):
                 got = R.tier(Lq, Lk, d)
-                s, n = want[t]
+                w, n = want[t]
                 four = Lq >= 65
                 assert got.tier == t
-                assert got.fwd == (f"mha_fwd{s}_kernel", n, d) and got.dq == (f"mha_bwd_dq{s}_kernel", n, d)
-                assert got.dkv == ("mha_bwd_dkv_split_kernel" if four else "mha_bwd_dkv_kernel", d)
-                assert got.both == ((f"mha_bwd_both{s}_kernel", n, d) if (t >= 3) == four else None)
+                assert got.fwd == ("mha_fwd_kernel", n, d, w) and got.dq == ("mha_bwd_dq_kernel", n, d, w)
+                assert got.dkv == ("mha_bwd_dkv_kernel", d, 4 if four else 1)
+                assert got.both == (("mha_bwd_both_kernel", n, d, w) if (t >= 3) == four else None)
     for bad in ((4, 513, 16), (4, 0, 16), (0, 4, 16), (4, 4, 24)):
         with pytest.raises(ValueError):
             R.tier(*bad)
@@ -65,7 +65,7 @@ def _coverage_gaps(tier_cases, single_cases):
         t = R.tier(c.Lq, c.Lk, c.d_k)
         if t.tier != c.tier:
             gaps.append(("row files under another tier", c, t.tier))
-        four = t.dkv[0] == "mha_bwd_dkv_split_kernel"
+        four = t.dkv[2] == 4
         seen.add((t.tier, c.d_k, four, c.mask))
         signatures.setdefault((t.tier, c.d_k, c.mask), set()).add((four, c.Lk % 4 == 0))
         if c.Lq % 4:
@@ -85,7 +85,7 @@ def _coverage_gaps(tier_cases, single_cases):
                     gaps.append(("family x (Lk % 4 == 0)", t, d, m, sorted(sig)))
             gaps += [("single launch", t, d, same) for same in (False, True) if (t, d, same) not in single]
     for d in R.D_KS:
-        gaps += [("Lq % 4 != 0", kern, d) for kern in ("mha_bwd_dkv_kernel", "mha_bwd_dkv_split_kernel") if (kern, d) not in ragged]
+        gaps += [("Lq % 4 != 0", "mha_bwd_dkv_kernel", d, w) for w in (1, 4) if ("mha_bwd_dkv_kernel", d, w) not in ragged]
     return gaps
 
 
@@ -116,7 +116,7 @@ def test_case_tables_cover_the_whole_grid(monkeypatch):
 
 
 def test_the_other_tables_sit_where_they_claim():
-    fam = lambda c: R.tier(c.Lq, c.Lk, c.d_k).dkv[0] == "mha_bwd_dkv_split_kernel"
+    fam = lambda c: R.tier(c.Lq, c.Lk, c.d_k).dkv[2] == 4
     for c in R.BIAS_CASES + R.DROPOUT_CASES + R.SCALAR_CASES + R.OFFSET_MASK_CASES:
         assert R.tier(c.Lq, c.Lk, c.d_k).tier == c.tier
     assert {(c.tier, fam(c)) for c in R.BIAS_CASES if c.d_k == 16} == {(t, f) for t in range(1, 6) for f in (False, True)}
