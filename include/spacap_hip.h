@@ -906,6 +906,22 @@ int spacap_beam_step_f32(const float *top_logp, const int32_t *top_word, long R,
 int spacap_beam_finish_f32(const float *score, const int32_t *len, const int8_t *trace_parent, const int32_t *trace_word, long R, int W,
                            int n_words, double alpha, int64_t *ys, float *best_score, int64_t *all_tokens, float *all_scores,
                            int32_t *all_len, spacap_stream_t stream);
+/* Sampled caption decoding (restated by tests/sampling_restated.py): one step's word choice for `rows`
+ * independent rows.  x, Wp, bias as for spacap_decode_word_f32 (the same logit arithmetic; no logits in HBM).  Row rho draws
+ * word `step` (0 <= step < n_words) as the first maximum over v of z_v = logit_v * inv_tau + g_v, with Gumbel noise
+ * g_v = -log(-log u), u = ((hash >> 9) + 0.5) 2^-23 and hash = the dropout keep mask's hash of the flat index
+ * (rho n_words + step) V + v under (seed, seed_dev) (seed_dev: a device word mixed in as for dropout, or NULL).  top_k = 0: over
+ * the whole vocabulary; 1 <= top_k <= min(8, V): over the top_k entries of spacap_beam_topw_f32 (run internally into the
+ * workspace), z from their log-probabilities.  logp = logit_word - logsumexp(logits), whatever inv_tau and top_k are.
+ * State, one entry per row, updated in place: a row with finished != 0 writes eos and keeps score and length; another adds logp
+ * to score (f32), sets length (i32) = step + 1, and sets finished (i32) when it drew eos.  ys i64 [rows][n_words] column `step`
+ * = the word; xw f32 [rows,128] = lut[word] * scale + pe_row, the next step's input rows (must not alias x).
+ * inv_tau finite and > 0; 0 <= eos < V.  workspace: device memory of spacap_sample_word_workspace_bytes(rows, V, top_k) bytes. */
+size_t spacap_sample_word_workspace_bytes(long rows, int V, int top_k);
+int spacap_sample_word_f32(const float *x, const void *Wp, const float *bias, long rows, int V, int top_k, float inv_tau, uint64_t seed,
+                           const uint64_t *seed_dev, int n_words, int step, int eos, const float *lut, float scale, const float *pe_row,
+                           int64_t *ys, float *score, int32_t *length, int32_t *finished, float *xw, void *workspace,
+                           spacap_stream_t stream);
 /* Split-K product for the skinny feed-forward products (K = d_ff, N = 128: w_2 forward, the data gradient through w_1):
  * out[s][r][n] = sum_{k in slice s} a[r][k] Wop[k][n], Wop[k][n] = trans_w ? W[n][k] (W [N,K]) : W[k][n] (W [K,N]);
  * a [R,K], K and N multiples of 128, nsplit a divisor of K / 128 (spacap_tf_gemm_splits suggests the one that fills the

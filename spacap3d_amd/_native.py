@@ -230,6 +230,8 @@ SIGNATURES = {
     "spacap_decode_attn_beam_f32": (_i, [_p, _p, _p, _p, _l, _i, _i, _i, _i, _i, _f, _p, _p]),
     "spacap_beam_step_f32": (_i, [_p, _p, _l, _i, _i, _i, _i, _i] + [_p] * 6 + [_p] * 4 + [_p, _f, _p, _p, _p]),
     "spacap_beam_finish_f32": (_i, [_p, _p, _p, _p, _l, _i, _i, ctypes.c_double, _p, _p, _p, _p, _p, _p]),
+    "spacap_sample_word_workspace_bytes": (ctypes.c_size_t, [_l, _i, _i]),
+    "spacap_sample_word_f32": (_i, [_p, _p, _p, _l, _i, _i, _f, _u64, _p, _i, _i, _i, _p, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
     "spacap_tf_gemm_splits": (_i, [_l, _i, _i]),
     "spacap_tf_gemm_f32": (_i, [_p, _p, _l, _i, _i, _i, _i, _p, _p]),
     "spacap_tf_dgrad_mask_f32": (_i, [_p, _p, _p, _f, _l, _i, _i, _p, _p]),

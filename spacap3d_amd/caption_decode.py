@@ -1,8 +1,9 @@
-"""Caption decoding on the device (csrc/caption_decode.hip): the greedy decoder and the beam search over the early-guide
-decoder stack, one token per row and step over pre-allocated key / value caches.  The layers themselves are the training
+"""Caption decoding on the device (csrc/caption_decode.hip): the greedy decoder, the beam search and sampled decoding over the
+early-guide decoder stack, one token per row and step over pre-allocated key / value caches.  The layers themselves are the training
 kernels of ``tf_layer`` with dropout off; what the two decoders share -- the per-call buffers and the launch sequence of one
 position -- is ``_Stack``, written once: a beam of width 1 must choose the greedy words bit for bit
-(tests/test_beam_search_gpu.py).  Each decoder keeps its own word selection, and the beam search its hypothesis state."""
+(tests/test_beam_search_gpu.py), and so must sampling with ``top_k`` = 1 (tests/test_sampling_gpu.py).  Each decoder keeps its
+own word selection, the beam search its hypothesis state and the sampler its row state."""
 import math
 
 import torch
@@ -213,3 +214,64 @@ def beam_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, beam_si
     if trace is not None:
         trace["parent"], trace["word"] = tr_parent, tr_word
     return (ys, best, beams, scores, lengths) if return_all else (ys, best)
+
+
+@torch.no_grad()
+def sample_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, num_samples=1, temperature=1.0, top_k=0, seed=None):
+    """Sampled decoding of R sequences, ``num_samples`` = S captions each (the reference decodes greedily
+    only): the ``greedy_decode`` loop at R S rows (row r S + s = sample s of sequence r; rows are independent, so the attention is
+    the greedy one and there is no ancestor table) with ``spacap_sample_word_f32`` as the word choice: the Gumbel-max draw from
+    softmax(logits / ``temperature``) over the whole vocabulary (``top_k`` = 0) or over the row's ``top_k`` <= 8 most probable
+    words, the log-probability of the drawn word under the model's own distribution, and the row state -- no logits in HBM.
+    ``seed``: an integer draws the same captions at every call; None takes the host word from ``attention._next_seed()`` and
+    mixes in the device word ``attention.rng_state``, so a captured graph draws new captions after every ``advance_rng``.  No step
+    reads a value back on the host.  Cache memory: 12 R S T 512 bytes for 6 layers.
+    Returns ``(ys (R, S, n_words) int64, score (R, S) float32, length (R, S) int32)``: the words (eos repeats after the first
+    eos), the summed log-probabilities through the first eos, and the position of the first eos plus one (``n_words``: none)."""
+    from .attention import _next_seed, rng_state
+    from .sampling import check_arguments
+    R, dev = indicator.shape[0], indicator.device
+    S, k, tau = int(num_samples), int(top_k), float(temperature)
+    T = n_words + 1
+    V = generator.proj.weight.shape[0]
+    check_arguments("sample_decode", S, tau, k, V)
+    RS = R * S
+    s = _Stack(dec, generator, embed, pe, RS, T, dev)
+    st = s.st
+    if seed is None:
+        seed_host, seed_dev = _next_seed(), rng_state(dev).data_ptr()
+    else:
+        seed_host, seed_dev = int(seed) & 0xFFFFFFFFFFFFFFFF, None
+
+    def attn(i, t):
+        check(lib.spacap_decode_attn_f32(s.qkv.data_ptr(), s.kc[i].data_ptr(), s.vc[i].data_ptr(), RS, s.h, s.dk, T, t, s.scale,
+                                         s.a.data_ptr(), st), "spacap_decode_attn_f32")
+
+    with torch.cuda.device(dev):
+        def cache_oom(e):
+            nl = len(s.layers)
+            need = 2 * nl * RS * T * D_MODEL * 4
+            raise RuntimeError(f"sample_decode: the key / value caches of {R} sequences x {S} samples need {need / 2**30:.2f} GiB "
+                               f"({nl} layers x 2 x {RS} rows x {T} positions x 512 B) and could not be allocated: "
+                               "decode fewer scenes per call or lower num_samples") from e
+
+        x = indicator.contiguous().repeat_interleave(S, 0) if S > 1 else indicator.contiguous()
+        s.allocate(on_cache_oom=cache_oom)
+        ws = torch.empty(int(lib.spacap_sample_word_workspace_bytes(RS, V, k)), dtype=torch.uint8, device=dev)
+        ys = torch.empty(RS, n_words, dtype=torch.long, device=dev)
+        score = torch.zeros(RS, dtype=torch.float32, device=dev)
+        length = torch.zeros(RS, dtype=torch.int32, device=dev)
+        fin = torch.zeros(RS, dtype=torch.int32, device=dev)
+        for t in range(T):
+            if t == 1:
+                x = s.sos_rows(sos)                         # every row starts with <sos>
+            elif t > 1:
+                x = s.xw
+            n = s.position(x, t, attn)
+            if t >= 1:
+                # word t - 1 of every row, its log-probability into the row's state, and xw = lut[word] sqrt(d) + pe[t]
+                check(lib.spacap_sample_word_f32(n.data_ptr(), s.gwp.data_ptr(), s.gb.data_ptr(), RS, V, k, 1.0 / tau, seed_host, seed_dev,
+                                                 n_words, t - 1, int(eos), s.lut.data_ptr(), s.sqrt_d,
+                                                 s.pe_rows[min(t, T - 1)].data_ptr(), ys.data_ptr(), score.data_ptr(), length.data_ptr(),
+                                                 fin.data_ptr(), s.xw.data_ptr(), ws.data_ptr(), st), "spacap_sample_word_f32")
+    return ys.view(R, S, n_words), score.view(R, S), length.view(R, S)

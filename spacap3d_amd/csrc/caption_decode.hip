@@ -9,7 +9,12 @@
 //       kernel's workgroup shape and logit tile with a sorted top-W list and an online (max, sum exp) per lane
 //   beam_step_kernel : one wave per sequence ranks the <= W W candidates by counting (score descending, then the smaller parent
 //       beam, then the smaller word) and writes the W survivors: state, ancestor table, trace, next input rows
-// and beam_finish_kernel backtracks the trace once at the end.  No logits reach HBM; no step reads a value back on the host.
+// and beam_finish_kernel backtracks the trace once at the end.  Sampled decoding (restated by
+// tests/sampling_restated.py) draws a word per row and step by the Gumbel-max rule:
+//   vocab_gumbel_kernel + sample_next_kernel : word = arg-max of logit / tau + Gumbel noise (the greedy kernel's workgroup shape
+//       and logit tile; the noise is a hash of (row, step, word)), its log-probability from an online (max, sum exp), the row's
+//       score / length / finished flag and the next input row; with top_k the candidates are beam_topw_kernel's k best
+// No logits reach HBM; no step reads a value back on the host.
 //
 // The logit tile -- row split, weight staging, the same six piece products in the same order on the same two accumulators -- the
 // first-maximum compare and the slicing of the vocabulary over workgroups are defined ONCE below: that is what makes a beam of
@@ -20,6 +25,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "dropout.hpp"
 #include "launch.hpp"
 #include "mfma.hpp"
 
@@ -531,6 +537,161 @@ __global__ __launch_bounds__(256) void beam_finish_kernel(const float *__restric
   }
 }
 
+// ---- sampled decoding: a word drawn per row and step ---------------------------------------------------------------------------
+// row rho draws word i as arg-max_v z_v, z_v = logit_v * (1 / tau) + g_v with Gumbel noise
+// g_v = -log(-log u), u = ((hash >> 9) + 0.5) 2^-23 in [2^-24, 1 - 2^-24] (exact in fp32), hash = the keep mask's hash32
+// (dropout.hpp) of the flat index (rho n_words + i) V + v: the arg-max is distributed as softmax(logit / tau).  Full-precision
+// logf: tests/sampling_restated.py restates g in numpy float32.
+__device__ __forceinline__ float gumbel_noise(unsigned long long idx, DropSeed sd) {
+  const float u = ((float)(hash32(idx, sd) >> 9) + 0.5f) * 1.1920928955078125e-07f;   // 2^-23
+  return -logf(-logf(u));
+}
+
+// vocab_argmax_kernel's grid, row split, staging and logit tile (the macros above).  Per lane and row: the running best
+// (z, word) under the first-maximum compare -- the lane's words arrive in increasing order --, the raw logit of that best, and
+// the online (max, sum exp) of the raw logits, as beam_topw_kernel keeps it.  After the last chunk the staging buffer is dead
+// and the merge aliases it (LDS stays at its 51 KB).  Per row and slice one partial (z, word, logit, max, sum); an empty slice
+// writes (-inf, NO_WORD, -inf, -inf, 0).  Words behind V - 1 (the staging repeats the last row) never pass `v < v_end`.
+__global__ __launch_bounds__(256) void vocab_gumbel_kernel(const float *__restrict__ x, const __bf16 *__restrict__ Wp, const float *__restrict__ bias,
+                                                           long R, int V, int per_slice, float inv_tau, unsigned long long seed,
+                                                           const unsigned long long *__restrict__ seed_dev, int n_words, int step,
+                                                           float *__restrict__ part_z, int *__restrict__ part_w, float *__restrict__ part_l,
+                                                           float *__restrict__ part_ms) {
+  __shared__ __attribute__((aligned(16))) __bf16 s_w[VA_STAGE_ELEMS];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
+  const long row0 = (long)blockIdx.x * VA_ROWS;
+  const int ns = gridDim.y, sl = blockIdx.y;
+  const int v_beg = sl * per_slice, v_end = min(V, v_beg + per_slice);
+  const DropSeed sd = make_seed(seed, seed_dev);
+  SPACAP_VA_SPLIT_ROWS();   // bf16x8 a[kc][piece]
+  float bz[4], bl[4], mx[4], sm[4];
+  int bi[4];
+  unsigned long long nbase[4];   // the noise index of word 0 of row row0 + 4 lg + u at this step
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    bz[u] = -INFINITY, bl[u] = -INFINITY, bi[u] = NO_WORD, mx[u] = -INFINITY, sm[u] = 0.f;
+    nbase[u] = ((unsigned long long)(row0 + 4 * lg + u) * (unsigned long long)n_words + (unsigned long long)step) * (unsigned long long)V;
+  }
+  SPACAP_VA_STAGING();      // stg, fetch(v0)
+  fetch(v_beg < V ? v_beg : 0);
+  for (int v0 = v_beg; v0 < v_end; v0 += VA_CHUNK) {
+    __syncthreads();
+    SPACAP_VA_STORE_STAGE();
+    __syncthreads();
+    if (v0 + VA_CHUNK < v_end) fetch(v0 + VA_CHUNK);
+    const int v = v0 + 16 * w + l15;                    // this lane's word of the chunk
+    SPACAP_VA_TILE();                                   // acc, acc2
+    if (v < v_end) {
+      const float bsv = bias[v];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float val = (acc[u] + acc2[u]) + bsv;     // (the greedy kernel's logit, bit for bit)
+        if (val > mx[u]) sm[u] = sm[u] * expf(mx[u] - val) + 1.f, mx[u] = val;
+        else sm[u] += expf(val - mx[u]);
+        const float z = val * inv_tau + gumbel_noise(nbase[u] + (unsigned long long)v, sd);
+        if (z > bz[u]) bz[u] = z, bi[u] = v, bl[u] = val;
+      }
+    }
+  }
+  __syncthreads();   // every wave is done with the last chunk: the staging buffer becomes the merge area
+  constexpr int MA = 4 * VA_ROWS * 17;                        // [4 waves][16 rows][16 lanes + 1]
+  float *s_z = reinterpret_cast<float *>(s_w);
+  int *s_i = reinterpret_cast<int *>(s_z + MA);
+  float *s_l = reinterpret_cast<float *>(s_i + MA), *s_m = s_l + MA, *s_s = s_m + MA;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int o = (w * VA_ROWS + 4 * lg + u) * 17 + l15;
+    s_z[o] = bz[u], s_i[o] = bi[u], s_l[o] = bl[u], s_m[o] = mx[u], s_s[o] = sm[u];
+  }
+  __syncthreads();
+  if (tid < 64) {
+    const int row = tid >> 2, ww = tid & 3;          // four threads per sequence, one wave's 16 lanes each
+    const int o = (ww * VA_ROWS + row) * 17;
+    float m = -INFINITY, ml = -INFINITY, M = -INFINITY, S = 0.f;
+    int mi = NO_WORD;
+#pragma unroll
+    for (int l = 0; l < 16; ++l) {
+      const float val = s_z[o + l];
+      const int idx = s_i[o + l];
+      if (SPACAP_FIRST_MAX(val, idx, m, mi)) m = val, mi = idx, ml = s_l[o + l];
+      M = fmaxf(M, s_m[o + l]);
+    }
+#pragma unroll
+    for (int l = 0; l < 16; ++l) {
+      const float lm = s_m[o + l];
+      S += lm == -INFINITY ? 0.f : s_s[o + l] * expf(lm - M);
+    }
+#pragma unroll
+    for (int q = 1; q <= 2; q <<= 1) {
+      const float om = __shfl_xor(m, q), ol = __shfl_xor(ml, q), oM = __shfl_xor(M, q), oS = __shfl_xor(S, q);
+      const int oi = __shfl_xor(mi, q);
+      if (SPACAP_FIRST_MAX(om, oi, m, mi)) m = om, mi = oi, ml = ol;
+      const float nM = fmaxf(M, oM);
+      S = (M == -INFINITY ? 0.f : S * expf(M - nM)) + (oM == -INFINITY ? 0.f : oS * expf(oM - nM));
+      M = nM;
+    }
+    if (ww == 0 && row0 + row < R) {
+      const size_t e = (size_t)(row0 + row) * ns + sl;
+      part_z[e] = m, part_w[e] = mi, part_l[e] = ml, part_ms[2 * e] = M, part_ms[2 * e + 1] = S;
+    }
+  }
+}
+
+// One row per 32 lanes, as decode_next_kernel.  top_k = 0: the slices' partials merged (first maximum of z; logp = (logit - M) -
+// log S).  top_k >= 1: the candidates are the row's k entries of top_logp / top_word (spacap_beam_topw_f32), perturbed by the
+// noise of their WORD: z = logp * (1 / tau) + g -- the log-probabilities are the logits minus one constant per row.  A finished
+// row writes eos and keeps score and length; another adds logp to its score, sets length = step + 1 and becomes finished when
+// it drew eos.  A row reads and writes its own state only.  xw[row] = lut[word] * scale + pe_row.
+__global__ __launch_bounds__(256) void sample_next_kernel(const float *__restrict__ part_z, const int *__restrict__ part_w,
+                                                          const float *__restrict__ part_l, const float *__restrict__ part_ms, int ns,
+                                                          const float *__restrict__ top_logp, const int *__restrict__ top_word, int top_k,
+                                                          float inv_tau, unsigned long long seed, const unsigned long long *__restrict__ seed_dev,
+                                                          long R, int V, int n_words, int step, int eos, const float *__restrict__ lut,
+                                                          float scale, const float *__restrict__ pe_row, long long *__restrict__ ys,
+                                                          float *score, int *length, int *fin, float *__restrict__ xw) {
+  const long r = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
+  const int c4 = threadIdx.x & 31;
+  if (r >= R) return;
+  float m = -INFINITY, logp = 0.f;
+  int mi = NO_WORD;
+  if (top_k == 0) {
+    float ml = -INFINITY, M = -INFINITY, S = 0.f;
+    for (int s = 0; s < ns; ++s) {
+      const size_t e = (size_t)r * ns + s;
+      const float val = part_z[e];
+      const int idx = part_w[e];
+      if (SPACAP_FIRST_MAX(val, idx, m, mi)) m = val, mi = idx, ml = part_l[e];
+      M = fmaxf(M, part_ms[2 * e]);
+    }
+    for (int s = 0; s < ns; ++s) {
+      const float pm = part_ms[2 * ((size_t)r * ns + s)];
+      S += pm == -INFINITY ? 0.f : part_ms[2 * ((size_t)r * ns + s) + 1] * expf(pm - M);
+    }
+    logp = (ml - M) - logf(S);
+  } else {
+    const DropSeed sd = make_seed(seed, seed_dev);
+    const unsigned long long nbase = ((unsigned long long)r * (unsigned long long)n_words + (unsigned long long)step) * (unsigned long long)V;
+    for (int k = 0; k < top_k; ++k) {
+      const float lp = top_logp[(size_t)r * top_k + k];
+      const int idx = top_word[(size_t)r * top_k + k];
+      const float val = lp * inv_tau + gumbel_noise(nbase + (unsigned long long)idx, sd);
+      if (SPACAP_FIRST_MAX(val, idx, m, mi)) m = val, mi = idx, logp = lp;
+    }
+  }
+  const int f = fin[r];
+  const int word = f ? eos : min(max(mi, 0), V - 1);
+  if (c4 == 0) {
+    ys[(size_t)r * n_words + step] = word;
+    if (!f) {
+      score[r] += logp;
+      length[r] = step + 1;
+      if (word == eos) fin[r] = 1;
+    }
+  }
+  const f32x4 e = ld4(lut + (size_t)word * VA_D + 4 * c4), p = ld4(pe_row + 4 * c4);
+  st4(xw + (size_t)r * VA_D + 4 * c4, f32x4{e[0] * scale + p[0], e[1] * scale + p[1], e[2] * scale + p[2], e[3] * scale + p[3]});
+}
+
 }  // namespace
 
 extern "C" int spacap_decode_attn_f32(const float *qkv, float *kcache, float *vcache, long R, int h, int d_k, int T, int t, float scale,
@@ -652,6 +813,61 @@ extern "C" int spacap_beam_finish_f32(const float *score, const int32_t *len, co
                      reinterpret_cast<const int *>(len), reinterpret_cast<const signed char *>(trace_parent),
                      reinterpret_cast<const int *>(trace_word), R, W, n_words, alpha, reinterpret_cast<long long *>(ys), best_score,
                      reinterpret_cast<long long *>(all_tokens), all_scores, reinterpret_cast<int *>(all_len));
+  SPACAP_CHECK_LAUNCH(what);
+  return SPACAP_OK;
+}
+
+/* Sampled decoding: one step's word choice for `rows` rows.  top_k = 0 draws from the whole vocabulary
+   (vocab_gumbel_kernel + sample_next_kernel); top_k >= 1 runs spacap_beam_topw_f32 into the workspace first and draws among its
+   k entries.  workspace: top_k = 0: the slices' partials, 20 bytes each; else spacap_beam_topw_f32's own workspace, then the
+   lists top_logp f32 [rows][k] and top_word i32 [rows][k]. */
+extern "C" size_t spacap_sample_word_workspace_bytes(long rows, int V, int top_k) {
+  if (rows <= 0 || V < 1 || top_k < 0 || top_k > BEAM_MAX || top_k > V) return 0;
+  if (top_k == 0) return (size_t)rows * va_slices(rows, V) * 20;
+  return spacap_beam_topw_workspace_bytes(rows, V, top_k) + (size_t)rows * top_k * 8;
+}
+
+extern "C" int spacap_sample_word_f32(const float *x, const void *Wp, const float *bias, long rows, int V, int top_k, float inv_tau,
+                                      uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos, const float *lut, float scale,
+                                      const float *pe_row, int64_t *ys, float *score, int32_t *length, int32_t *finished, float *xw,
+                                      void *workspace, spacap_stream_t stream) {
+  const char *what = "spacap_sample_word_f32";
+  SPACAP_REQUIRE(rows >= 0 && V >= 1, "%s: (rows=%ld, V=%d) unsupported: rows >= 0 and V >= 1", what, rows, V);
+  SPACAP_REQUIRE(top_k >= 0 && top_k <= BEAM_MAX && top_k <= V, "%s: top_k=%d unsupported: 0 <= top_k <= min(%d, V=%d)", what, top_k,
+                 BEAM_MAX, V);
+  SPACAP_REQUIRE(isfinite(inv_tau) && inv_tau > 0.f, "%s: 1/temperature = %g must be finite and positive", what, (double)inv_tau);
+  SPACAP_REQUIRE(n_words >= 1 && step >= 0 && step < n_words, "%s: (n_words=%d, step=%d) unsupported: 0 <= step < n_words", what, n_words, step);
+  SPACAP_REQUIRE(eos >= 0 && eos < V, "%s: eos=%d outside the vocabulary (V=%d)", what, eos, V);
+  if (rows == 0) return SPACAP_OK;
+  SPACAP_REQUIRE(x && Wp && bias && lut && pe_row && ys && score && length && finished && xw && workspace, "%s: null pointer", what);
+  SPACAP_REQUIRE(aligned16(x, Wp, lut, pe_row, xw), "%s: x, Wp, lut, pe_row and xw must be 16-byte aligned", what);
+  SPACAP_REQUIRE(rows <= 2147483647L, "%s: too many rows", what);
+  hipStream_t s = spacap::as_stream(stream);
+  const unsigned long long *sdev = reinterpret_cast<const unsigned long long *>(seed_dev);
+  const float *pz = nullptr, *pl = nullptr, *pms = nullptr, *top_lp = nullptr;
+  const int *pw = nullptr, *top_wd = nullptr;
+  int ns = 0;
+  if (top_k == 0) {
+    ns = va_slices(rows, V);
+    const int per = va_per_slice(V, ns);
+    float *wz = static_cast<float *>(workspace);
+    int *ww = reinterpret_cast<int *>(wz + (size_t)rows * ns);
+    float *wl = reinterpret_cast<float *>(ww + (size_t)rows * ns), *wms = wl + (size_t)rows * ns;
+    hipLaunchKernelGGL(vocab_gumbel_kernel, dim3((unsigned)((rows + VA_ROWS - 1) / VA_ROWS), ns), dim3(256), 0, s, x,
+                       static_cast<const __bf16 *>(Wp), bias, rows, V, per, inv_tau, (unsigned long long)seed, sdev, n_words, step, wz, ww, wl,
+                       wms);
+    pz = wz, pw = ww, pl = wl, pms = wms;
+  } else {
+    char *base = static_cast<char *>(workspace);
+    float *lp = reinterpret_cast<float *>(base + spacap_beam_topw_workspace_bytes(rows, V, top_k));
+    int32_t *wd = reinterpret_cast<int32_t *>(lp + (size_t)rows * top_k);
+    const int rc = spacap_beam_topw_f32(x, Wp, bias, rows, V, top_k, lp, wd, workspace, stream);
+    if (rc != SPACAP_OK) return rc;
+    top_lp = lp, top_wd = reinterpret_cast<const int *>(wd);
+  }
+  hipLaunchKernelGGL(sample_next_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, s, pz, pw, pl, pms, ns, top_lp, top_wd, top_k, inv_tau,
+                     (unsigned long long)seed, sdev, rows, V, n_words, step, eos, lut, scale, pe_row, reinterpret_cast<long long *>(ys), score,
+                     reinterpret_cast<int *>(length), reinterpret_cast<int *>(finished), xw);
   SPACAP_CHECK_LAUNCH(what);
   return SPACAP_OK;
 }

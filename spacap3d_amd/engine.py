@@ -754,10 +754,15 @@ class Evaluator:
 
     ``beam_size`` / ``length_penalty``: set the captioner's decoding attributes (``beam_size`` > 1: beam search instead of
     greedy decoding, the forward then also returns ``lang_cap_score``).  ``lang_cap`` keeps its shape and
-    meaning, so ``caption_eval``, ``predictions`` and ``detection_ap`` consume it unchanged."""
+    meaning, so ``caption_eval``, ``predictions`` and ``detection_ap`` consume it unchanged.
+
+    ``sample``: ``dict(num_samples=S, temperature=tau, top_k=k, seed=None)`` (every key optional; exclusive with ``beam_size`` >
+    1): sampled decoding instead (DESIGN.md section 7i) -- sets the captioner's ``num_samples`` / ``temperature`` / ``top_k``;
+    ``lang_cap`` is sample 0 and the forward also returns ``lang_cap_score``, ``lang_cap_samples``, ``lang_cap_sample_scores``
+    and ``lang_cap_sample_lengths``.  ``seed``: an integer repeats the same draws at every call; None draws new ones."""
 
     def __init__(self, model, graph=True, postprocess=None, detection_ap=None, caption_eval=None, predictions=None, beam_size=None,
-                 length_penalty=None):
+                 length_penalty=None, sample=None):
         self.model = model
         # decoding attributes of the captioner (transformer_captioner.TransformerDecoderModel); None leaves what it has
         cap = getattr(model, "caption", None)
@@ -770,6 +775,19 @@ class Evaluator:
                 cap.beam_size = int(beam_size)
             if length_penalty is not None:
                 cap.length_penalty = float(length_penalty)
+        if sample is not None:
+            if cap is None or not hasattr(cap, "num_samples"):
+                raise ValueError("Evaluator: sample needs a model with a Transformer captioner")
+            unknown = set(sample) - {"num_samples", "temperature", "top_k", "seed"}
+            if unknown:
+                raise ValueError(f"Evaluator: sample has unknown keys {sorted(unknown)}")
+            if int(cap.beam_size) > 1:
+                raise ValueError("Evaluator: sample and beam_size > 1 exclude each other")
+            S, tau, k = int(sample.get("num_samples", 1)), float(sample.get("temperature", 1.0)), int(sample.get("top_k", 0))
+            from .sampling import check_arguments
+            check_arguments("Evaluator: sample", S, tau, k, cap.model.generator.proj.out_features)
+            cap.num_samples, cap.temperature, cap.top_k = S, tau, k
+            cap.sample_seed = None if sample.get("seed") is None else int(sample["seed"])
         self.post_kw = None
         for name, given in (("predictions", predictions), ("detection_ap", detection_ap), ("caption_eval", caption_eval)):
             if given is not None and postprocess is None:

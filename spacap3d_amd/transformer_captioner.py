@@ -588,8 +588,18 @@ class TransformerDecoderModel(nn.Module):
     beam_return_all = False
     beam_generic = False
     last_beam_trace = None
+    # Sampled decoding, set the same way: num_samples = S >= 1 draws S captions per proposal from
+    # softmax(logits / temperature), over the whole vocabulary (top_k = 0) or the top_k <= 8 most probable words; 0 = off.
+    # sample_generic sends it through sampling.sample (parity tests); last_sample_trace then holds its per-step gaps.
+    num_samples = 0
+    temperature = 1.0
+    top_k = 0
+    sample_generic = False
+    sample_seed = None          # an integer: the same draws at every call (forward_eval's sample_seed, when that is None)
+    last_sample_trace = None
 
-    def forward_eval(self, ep, use_cache=True, beam_size=None, length_penalty=None):
+    def forward_eval(self, ep, use_cache=True, beam_size=None, length_penalty=None, num_samples=None, temperature=None, top_k=None,
+                     sample_seed=None):
         """Greedy decoding of B*K captions (:402-453).  The reference re-runs the 6-layer encoder AND the whole
         decoder prefix at each of the 31 steps; the encoder output does not depend on the words (computed once),
         and with ``use_cache`` the decoder keeps the keys / values of earlier positions so that each step only
@@ -600,7 +610,15 @@ class TransformerDecoderModel(nn.Module):
         -- ``lang_cap`` (B, K, n_words) holds the winners' words (eos repeats after the first eos), ``lang_cap_score`` (B, K)
         their summed log-probabilities, and with ``beam_return_all`` ``lang_cap_beams`` (B, K, W, n_words),
         ``lang_cap_beam_scores`` and ``lang_cap_beam_lengths`` (B, K, W) every final hypothesis.  The winner maximises
-        score / length ** ``length_penalty``."""
+        score / length ** ``length_penalty``.
+
+        ``num_samples`` = S >= 1 (default: the module attribute, 0 = off): sampled decoding instead (the reference has none;
+        DESIGN.md section 7i) -- S captions per proposal drawn from softmax(logits / ``temperature``), over the whole vocabulary
+        (``top_k`` = 0) or the ``top_k`` <= 8 most probable words.  ``lang_cap`` (B, K, n_words) is sample 0 (eos repeats after
+        the first eos) and ``lang_cap_score`` (B, K) its summed log-probability under the model's own distribution;
+        ``lang_cap_samples`` (B, K, S, n_words), ``lang_cap_sample_scores`` and ``lang_cap_sample_lengths`` (B, K, S) hold every
+        sample.  ``sample_seed``: an integer draws the same captions at every call; None draws new ones per call and, in a
+        captured graph, after every ``attention.advance_rng``."""
         W = int(self.beam_size if beam_size is None else beam_size)
         alpha = float(self.length_penalty if length_penalty is None else length_penalty)
         if W < 1:
@@ -608,6 +626,19 @@ class TransformerDecoderModel(nn.Module):
         beam = W > 1 or self.beam_generic
         if beam and not use_cache:
             raise ValueError("forward_eval: beam search keeps key / value caches (use_cache=False is the greedy parity path)")
+        S = int(self.num_samples if num_samples is None else num_samples)
+        tau = float(self.temperature if temperature is None else temperature)
+        topk = int(self.top_k if top_k is None else top_k)
+        sample_seed = self.sample_seed if sample_seed is None else sample_seed
+        if S < 0 or (S < 1 and num_samples is not None):      # (the attribute's 0 means off; an argument asks for samples)
+            raise ValueError(f"forward_eval: num_samples {S} < 1")
+        if S >= 1:
+            from .sampling import check_arguments
+            if W > 1:
+                raise ValueError("forward_eval: sampling and beam search (beam_size > 1) exclude each other")
+            check_arguments("forward_eval", S, tau, topk, self.model.generator.proj.out_features)
+            if not use_cache:
+                raise ValueError("forward_eval: sampling keeps key / value caches (use_cache=False is the greedy parity path)")
         obj_features = ep["aggregated_vote_features"]
         if self.token_proj is not None:
             obj_features = self.token_proj(obj_features)
@@ -647,6 +678,15 @@ class TransformerDecoderModel(nn.Module):
         cd = getattr(ops(), "caption_decode", None)
         fused = self.early_guide and not self.training and cd is not None \
             and cd.decode_supported(dec.layers, indicator.squeeze(1), MAX_DES_LEN + 1)
+        if S >= 1:
+            sos, eos = self.word_to_idx["sos"], self.word_to_idx["eos"]
+            if fused and not self.sample_generic:
+                # the greedy loop below at B K S rows with a drawn word in place of the arg-max (caption_decode.sample_decode)
+                self.last_sample_trace = None
+                got = cd.sample_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), sos, eos, MAX_DES_LEN + 1,
+                                       S, tau, topk, sample_seed)
+                return self._sample_outputs(ep, B, K, *got)
+            return self._sample_generic(ep, B, K, S, tau, topk, sample_seed, dec, indicator, embed, pos)
         if beam and fused and not self.beam_generic:
             # the greedy loop below at B K W rows: top-W log-probabilities, one selection per sequence, attention through an
             # ancestor table (caption_decode.beam_decode, csrc/caption_decode.hip)
@@ -690,6 +730,42 @@ class TransformerDecoderModel(nn.Module):
             ep["lang_cap_beam_scores"] = scores.view(B, K, -1)
             ep["lang_cap_beam_lengths"] = lengths.view(B, K, -1)
         return ep
+
+    def _sample_outputs(self, ep, B, K, ys, score, length):
+        ep["lang_cap"] = ys[:, 0].reshape(B, K, -1)
+        ep["lang_cap_score"] = score[:, 0].reshape(B, K)
+        ep["lang_cap_samples"] = ys.view(B, K, ys.shape[1], -1)
+        ep["lang_cap_sample_scores"] = score.view(B, K, -1)
+        ep["lang_cap_sample_lengths"] = length.view(B, K, -1)
+        return ep
+
+    def _sample_generic(self, ep, B, K, S, tau, topk, seed, dec, indicator, embed, pos):
+        """Sampled decoding through the cached per-operator decoder (``decode_incremental``): everything the fused path does not
+        take -- late guide, other head counts, the CPU oracle backend.  Row r S + s is sample s of sequence r."""
+        from .sampling import sample
+        R = B * K
+        ind = indicator.repeat_interleave(S, 0)
+        caches = [dict() for _ in dec.layers]
+        cross_mem = None if self.early_guide else ind
+        seed_dev = None
+        if seed is None:   # as the fused path: a host word per call and the device's step counter
+            from .attention import _next_seed, rng_state
+            seed = _next_seed()
+            seed_dev = rng_state(ind.device) if ind.is_cuda else None
+
+        def step_fn(i, words):
+            x_new = pos.dropout(embed(words.unsqueeze(1)) + pos.pe[:, i:i + 1])
+            mask = None
+            if i == 0 and self.early_guide:   # positions: 0 = object indicator, 1 = sos
+                x_new = torch.cat((ind, x_new), dim=1)
+                mask = subsequent_mask(2, device=words.device).expand(R * S, -1, -1)
+            out = decode_incremental(dec, x_new, caches, memory=cross_mem, src_mask=None, mask=mask)
+            return self.model.generator.proj(out[:, -1, :])
+
+        got = sample(step_fn, R, S, MAX_DES_LEN + 1, self.word_to_idx["sos"], self.word_to_idx["eos"], tau, topk, seed, seed_dev,
+                     device=indicator.device)
+        self.last_sample_trace = {"gap": got["gap"]}     # (n_words, R S): for parity tests
+        return self._sample_outputs(ep, B, K, got["ys"], got["score"], got["length"])
 
     def _beam_generic(self, ep, B, K, W, alpha, dec, indicator, embed, pos):
         """Beam search through the cached per-operator decoder (``decode_incremental``): everything the fused path does not
