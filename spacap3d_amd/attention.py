@@ -100,32 +100,91 @@ def mha_args(q_ptr, k_ptr, v_ptr, q_strides, k_strides, v_strides, mask_u8, mask
             rng_state(device).data_ptr() if dropout_p > 0.0 else None)
 
 
+class Operands:
+    """Where the attention kernels read q, k, v -- three pointers and three (scene, head, row) stride triples -- and where their
+    backward writes dq, dk, dv (``grads``): three tensors, or the three column blocks of one packed projection."""
+
+    def __init__(self, ptrs, strides, B, h, Lq, Lk, dk, device, packed):
+        self.ptrs, self.strides, self.device, self.packed = ptrs, strides, device, packed
+        self.B, self.h, self.Lq, self.Lk, self.dk = B, h, Lq, Lk, dk
+        self.scale = 1.0 / math.sqrt(dk)
+
+    @staticmethod
+    def separate(q, k, v):
+        """q (B,h,Lq,d_k), k, v (B,h,Lk,d_k), last dimension dense."""
+        B, h, Lq, dk = q.shape
+        return Operands((q.data_ptr(), k.data_ptr(), v.data_ptr()), (_strides3(q), _strides3(k), _strides3(v)), B, h, Lq, k.shape[2],
+                        dk, q.device, None)
+
+    @staticmethod
+    def packed(qkv, h):
+        """qkv (B, L, 3*h*d_k) = [q | k | v], contiguous."""
+        B, L, three_hd = qkv.shape
+        hd = three_hd // 3
+        base, es, strides = qkv.data_ptr(), qkv.element_size(), (L * three_hd, hd // h, three_hd)
+        return Operands((base, base + hd * es, base + 2 * hd * es), (strides,) * 3, B, h, L, L, hd // h, qkv.device, qkv)
+
+    def args(self, mask, bias, dropout_p, seed):
+        """``mha_args`` of these operands; ``mask`` = (mask_u8, mask_sb, mask_sq) of ``_prep_mask``."""
+        return mha_args(*self.ptrs, *self.strides, *mask, bias, self.B, self.h, self.Lq, self.Lk, self.dk, self.scale, dropout_p,
+                        seed, self.device)
+
+    def grads(self):
+        """Fresh gradient buffers: (the tensors, their three pointers, the row stride of the packed layout or 0 for dense
+        (B, L, h, d_k) ones)."""
+        if self.packed is not None:
+            dqkv = torch.empty_like(self.packed)
+            gb, step = dqkv.data_ptr(), self.h * self.dk * dqkv.element_size()
+            return (dqkv,), (gb, gb + step, gb + 2 * step), dqkv.shape[2]
+        g = tuple(torch.empty(self.B, L, self.h, self.dk, dtype=torch.float32, device=self.device) for L in (self.Lq, self.Lk, self.Lk))
+        return g, tuple(t.data_ptr() for t in g), 0
+
+
+def mha_forward(o, mask, bias, dropout_p, seed, need_p):
+    """One launch of spacap_mha_fwd_f32: (out (B,Lq,h,d_k), p (B,h,Lq,Lk) or None, the row statistics (B,h,Lq,2) = (max, sum))."""
+    with torch.cuda.device(o.device):
+        out = torch.empty(o.B, o.Lq, o.h, o.dk, dtype=torch.float32, device=o.device)
+        p = torch.empty(o.B, o.h, o.Lq, o.Lk, dtype=torch.float32, device=o.device) if need_p else None
+        lse = torch.empty(o.B, o.h, o.Lq, 2, dtype=torch.float32, device=o.device)
+        check(lib.spacap_mha_fwd_f32(*o.args(mask, bias, dropout_p, seed), out.data_ptr(), p.data_ptr() if need_p else None,
+                                     lse.data_ptr(), torch.cuda.current_stream(o.device).cuda_stream), "spacap_mha_fwd_f32")
+    return out, p, lse
+
+
+def mha_backward(o, mask, bias, dropout_p, seed, lse, d_out, d_p):
+    """One call of spacap_mha_bwd_f32 for d_out (B,Lq,h,d_k) (any strides) and the optional gradient d_p of the attention map:
+    the tensors of ``o.grads()``."""
+    with torch.cuda.device(o.device):
+        d_out_c = d_out.contiguous()
+        d_p_c = d_p.contiguous() if d_p is not None else None
+        g, gptrs, ld = o.grads()
+        ws = torch.empty(max(int(lib.spacap_mha_bwd_workspace_bytes(o.B, o.h, o.Lq)), 16), dtype=torch.uint8, device=o.device)
+        check(lib.spacap_mha_bwd_f32(*o.args(mask, bias, dropout_p, seed), lse.data_ptr(), d_out_c.data_ptr(),
+                                     d_p_c.data_ptr() if d_p_c is not None else None, ws.data_ptr(), *gptrs, ld,
+                                     torch.cuda.current_stream(o.device).cuda_stream), "spacap_mha_bwd_f32")
+    return g
+
+
+def mha_backward_delta(o, mask, dropout_p, seed, lse, d_out, delta):
+    """One launch of spacap_mha_bwd_delta_f32 (dQ and dK / dV halves side by side) for a dense d_out whose row term
+    delta[b, head, q] = sum_d out d_out the caller already has (tf_layer.AttnFfn1): the tensors of ``o.grads()``."""
+    with torch.cuda.device(o.device):
+        g, gptrs, ld = o.grads()
+        check(lib.spacap_mha_bwd_delta_f32(*o.args(mask, None, dropout_p, seed), lse.data_ptr(), d_out.data_ptr(), delta.data_ptr(),
+                                           *gptrs, ld, torch.cuda.current_stream(o.device).cuda_stream), "spacap_mha_bwd_delta_f32")
+    return g
+
+
 class FusedAttention(Function):
     @staticmethod
     def forward(ctx, q, k, v, mask_u8, mask_sb, mask_sq, bias, dropout_p, seed, need_p):
         if not q.is_cuda:
             raise RuntimeError("CPU not supported")
-        B, h, Lq, dk = q.shape
-        Lk = k.shape[2]
-        if q.stride(3) != 1:
-            q = q.contiguous()
-        if k.stride(3) != 1:
-            k = k.contiguous()
-        if v.stride(3) != 1:
-            v = v.contiguous()
-        scale = 1.0 / math.sqrt(dk)
-        with torch.cuda.device(q.device):
-            out = torch.empty(B, Lq, h, dk, dtype=torch.float32, device=q.device)
-            p = torch.empty(B, h, Lq, Lk, dtype=torch.float32, device=q.device) if need_p else None
-            lse = torch.empty(B, h, Lq, 2, dtype=torch.float32, device=q.device)  # (row max, row sum)
-            check(lib.spacap_mha_fwd_f32(
-                *mha_args(q.data_ptr(), k.data_ptr(), v.data_ptr(), _strides3(q), _strides3(k), _strides3(v), mask_u8, mask_sb,
-                          mask_sq, bias, B, h, Lq, Lk, dk, scale, dropout_p, seed, q.device),
-                out.data_ptr(), p.data_ptr() if need_p else None, lse.data_ptr(),
-                torch.cuda.current_stream(q.device).cuda_stream), "spacap_mha_fwd_f32")
+        q, k, v = (t if t.stride(3) == 1 else t.contiguous() for t in (q, k, v))
+        out, p, lse = mha_forward(Operands.separate(q, k, v), (mask_u8, mask_sb, mask_sq), bias, dropout_p, seed, need_p)
         ctx.save_for_backward(q, k, v, mask_u8, bias, lse)
         ctx.set_materialize_grads(False)   # no zero tensor for the unused second output's gradient
-        ctx.meta = (mask_sb, mask_sq, dropout_p, seed, scale, need_p)
+        ctx.meta = (mask_sb, mask_sq, dropout_p, seed, need_p)
         out_v = out.transpose(1, 2)
         if need_p:
             return out_v, p
@@ -135,27 +194,12 @@ class FusedAttention(Function):
     @staticmethod
     def backward(ctx, d_out, d_p):
         q, k, v, mask_u8, bias, lse = ctx.saved_tensors
-        mask_sb, mask_sq, dropout_p, seed, scale, need_p = ctx.meta
-        B, h, Lq, dk = q.shape
-        Lk = k.shape[2]
+        mask_sb, mask_sq, dropout_p, seed, need_p = ctx.meta
         if d_out is None:   # only the attention map was used downstream
-            d_out = torch.zeros(B, h, Lq, dk, dtype=torch.float32, device=q.device)
-        with torch.cuda.device(q.device):
-            d_out_c = d_out.transpose(1, 2).contiguous()  # (B, Lq, h, dk)
-            d_p_c = d_p.contiguous() if (need_p and d_p is not None) else None
-            dq = torch.empty(B, Lq, h, dk, dtype=torch.float32, device=q.device)
-            dk_ = torch.empty(B, Lk, h, dk, dtype=torch.float32, device=q.device)
-            dv = torch.empty(B, Lk, h, dk, dtype=torch.float32, device=q.device)
-            ws = torch.empty(max(int(lib.spacap_mha_bwd_workspace_bytes(B, h, Lq)), 16), dtype=torch.uint8,
-                             device=q.device)
-            check(lib.spacap_mha_bwd_f32(
-                *mha_args(q.data_ptr(), k.data_ptr(), v.data_ptr(), _strides3(q), _strides3(k), _strides3(v), mask_u8, mask_sb,
-                          mask_sq, bias, B, h, Lq, Lk, dk, scale, dropout_p, seed, q.device),
-                lse.data_ptr(), d_out_c.data_ptr(), d_p_c.data_ptr() if d_p_c is not None else None, ws.data_ptr(),
-                dq.data_ptr(), dk_.data_ptr(), dv.data_ptr(), 0,
-                torch.cuda.current_stream(q.device).cuda_stream), "spacap_mha_bwd_f32")
-        return (dq.transpose(1, 2), dk_.transpose(1, 2), dv.transpose(1, 2), None, None, None, None, None, None,
-                None)
+            d_out = torch.zeros(q.shape, dtype=torch.float32, device=q.device)
+        dq, dk, dv = mha_backward(Operands.separate(q, k, v), (mask_u8, mask_sb, mask_sq), bias, dropout_p, seed, lse,
+                                  d_out.transpose(1, 2), d_p if need_p else None)
+        return (dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None, None, None, None, None)
 
 
 class FusedSelfAttentionPacked(Function):
@@ -169,25 +213,11 @@ class FusedSelfAttentionPacked(Function):
         if not qkv.is_cuda:
             raise RuntimeError("CPU not supported")
         qkv = qkv.contiguous()
-        B, L, three_hd = qkv.shape
-        hd = three_hd // 3
-        dk = hd // h
-        scale = 1.0 / math.sqrt(dk)
-        es = qkv.element_size()
-        strides = (L * three_hd, dk, three_hd)
-        with torch.cuda.device(qkv.device):
-            out = torch.empty(B, L, hd, dtype=torch.float32, device=qkv.device)
-            p = torch.empty(B, h, L, L, dtype=torch.float32, device=qkv.device) if need_p else None
-            lse = torch.empty(B, h, L, 2, dtype=torch.float32, device=qkv.device)
-            base = qkv.data_ptr()
-            check(lib.spacap_mha_fwd_f32(
-                *mha_args(base, base + hd * es, base + 2 * hd * es, strides, strides, strides, mask_u8, mask_sb, mask_sq, None,
-                          B, h, L, L, dk, scale, dropout_p, seed, qkv.device),
-                out.data_ptr(), p.data_ptr() if need_p else None, lse.data_ptr(),
-                torch.cuda.current_stream(qkv.device).cuda_stream), "spacap_mha_fwd_f32")
+        out, p, lse = mha_forward(Operands.packed(qkv, h), (mask_u8, mask_sb, mask_sq), None, dropout_p, seed, need_p)
         ctx.save_for_backward(qkv, mask_u8, lse)
         ctx.set_materialize_grads(False)   # no zero tensor for the unused second output's gradient
-        ctx.meta = (h, mask_sb, mask_sq, dropout_p, seed, scale, need_p)
+        ctx.meta = (h, mask_sb, mask_sq, dropout_p, seed, need_p)
+        out = out.view(qkv.shape[0], qkv.shape[1], -1)
         if need_p:
             return out, p
         ctx.mark_non_differentiable(lse)
@@ -196,27 +226,11 @@ class FusedSelfAttentionPacked(Function):
     @staticmethod
     def backward(ctx, d_out, d_p):
         qkv, mask_u8, lse = ctx.saved_tensors
-        h, mask_sb, mask_sq, dropout_p, seed, scale, need_p = ctx.meta
-        B, L, three_hd = qkv.shape
-        hd = three_hd // 3
-        dk = hd // h
-        es = qkv.element_size()
-        strides = (L * three_hd, dk, three_hd)
+        h, mask_sb, mask_sq, dropout_p, seed, need_p = ctx.meta
         if d_out is None:   # only the attention map was used downstream
-            d_out = torch.zeros(B, L, hd, dtype=torch.float32, device=qkv.device)
-        with torch.cuda.device(qkv.device):
-            d_out_c = d_out.contiguous()
-            d_p_c = d_p.contiguous() if (need_p and d_p is not None) else None
-            dqkv = torch.empty_like(qkv)
-            ws = torch.empty(max(int(lib.spacap_mha_bwd_workspace_bytes(B, h, L)), 16), dtype=torch.uint8,
-                             device=qkv.device)
-            base, gb = qkv.data_ptr(), dqkv.data_ptr()
-            check(lib.spacap_mha_bwd_f32(
-                *mha_args(base, base + hd * es, base + 2 * hd * es, strides, strides, strides, mask_u8, mask_sb, mask_sq, None,
-                          B, h, L, L, dk, scale, dropout_p, seed, qkv.device),
-                lse.data_ptr(), d_out_c.data_ptr(), d_p_c.data_ptr() if d_p_c is not None else None, ws.data_ptr(),
-                gb, gb + hd * es, gb + 2 * hd * es, three_hd,
-                torch.cuda.current_stream(qkv.device).cuda_stream), "spacap_mha_bwd_f32")
+            d_out = torch.zeros(qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3, dtype=torch.float32, device=qkv.device)
+        (dqkv,) = mha_backward(Operands.packed(qkv, h), (mask_u8, mask_sb, mask_sq), None, dropout_p, seed, lse, d_out,
+                               d_p if need_p else None)
         return dqkv, None, None, None, None, None, None, None
 
 
@@ -247,7 +261,6 @@ def _ln_backward(xc, a, stats, dyc, add, eps):
     """dx, da, db of the LayerNorm; the (da, db) column sums over the workgroup partials go through ``sum_slabs``
     (same 4-group order as the library's own reduction kernel) so that a training step can batch them with the
     weight-gradient sums (deferred_slab_sums)."""
-    from ._native import sum_slabs
     D = xc.shape[-1]
     rows = xc.numel() // D
     with torch.cuda.device(xc.device):
@@ -275,44 +288,13 @@ def _ln_backward(xc, a, stats, dyc, add, eps):
 
 class FusedLayerNorm(Function):
     """a * (x - mean) / (std_unbiased + eps) + b  (models/transformer_captioner.py:102-113) in one launch
-    forward and two backward (spacap_layernorm_*_f32)."""
-
-    @staticmethod
-    def forward(ctx, x, a, b, eps):
-        if not x.is_cuda:
-            raise RuntimeError("CPU not supported")
-        xc = x.contiguous()
-        D = xc.shape[-1]
-        rows = xc.numel() // D
-        with torch.cuda.device(x.device):
-            y = torch.empty_like(xc)
-            stats = torch.empty(rows, 2, dtype=torch.float32, device=x.device)
-            check(lib.spacap_layernorm_fwd_f32(xc.data_ptr(), a.data_ptr(), b.data_ptr(), rows, D, float(eps),
-                                               y.data_ptr(), stats.data_ptr(),
-                                               torch.cuda.current_stream(x.device).cuda_stream), "spacap_layernorm_fwd_f32")
-        ctx.save_for_backward(xc, a, stats)
-        ctx.eps = float(eps)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        xc, a, stats = ctx.saved_tensors
-        dx, da, db = _ln_backward(xc, a, stats, dy.contiguous(), None, ctx.eps)
-        return dx, da, db, None
-
-
-def layer_norm(x, a, b, eps=1e-6):
-    return FusedLayerNorm.apply(x, a, b, eps)
-
-
-class FusedLayerNormResidual(Function):
-    """(norm(x), x) for the pre-norm residual block ``x + dropout(sublayer(norm(x)))``
-    (models/transformer_captioner.py:115-123): the second output is x itself, to be used as the residual operand, so
+    forward and two backward (spacap_layernorm_*_f32).  With ``residual``: (norm(x), x) for the pre-norm residual block
+    ``x + dropout(sublayer(norm(x)))`` (:115-123) -- the second output is x itself, to be used as the residual operand, so
     that BOTH gradient paths into x arrive at this node and the backward kernel adds them while it writes dx
-    (spacap_layernorm_bwd_add_f32) -- otherwise autograd sums them with one more pass per sub-layer."""
+    (spacap_layernorm_bwd_add_f32); otherwise autograd sums them with one more pass per sub-layer."""
 
     @staticmethod
-    def forward(ctx, x, a, b, eps):
+    def forward(ctx, x, a, b, eps, residual):
         if not x.is_cuda:
             raise RuntimeError("CPU not supported")
         xc = x.contiguous()
@@ -326,102 +308,32 @@ class FusedLayerNormResidual(Function):
                                                torch.cuda.current_stream(x.device).cuda_stream), "spacap_layernorm_fwd_f32")
         ctx.save_for_backward(xc, a, stats)
         ctx.eps = float(eps)
+        if not residual:
+            return y
         ctx.set_materialize_grads(False)
         return y, xc.view_as(xc)
 
     @staticmethod
-    def backward(ctx, dy, dres):
+    def backward(ctx, dy, dres=None):
         xc, a, stats = ctx.saved_tensors
-        if dy is None:
-            return dres, None, None, None
+        if dy is None:      # (residual form only: the norm was not used downstream)
+            return dres, None, None, None, None
         dx, da, db = _ln_backward(xc, a, stats, dy.contiguous(), dres.contiguous() if dres is not None else None, ctx.eps)
-        return dx, da, db, None
+        return dx, da, db, None, None
+
+
+def layer_norm(x, a, b, eps=1e-6):
+    return FusedLayerNorm.apply(x, a, b, eps, False)
 
 
 def layer_norm_residual(x, a, b, eps=1e-6):
-    """(norm(x), residual operand) -- see FusedLayerNormResidual."""
-    return FusedLayerNormResidual.apply(x, a, b, eps)
+    """(norm(x), residual operand) -- see FusedLayerNorm."""
+    return FusedLayerNorm.apply(x, a, b, eps, True)
 
 
-class RelationFeature(Function):
-    """R[b,i,j,h*D+d] = P[b,h,i,j] * V[b,h,j,d]  (models/transformer_captioner.py:393-396) in one launch each way."""
-
-    @staticmethod
-    def forward(ctx, P, V):
-        if not P.is_cuda:
-            raise RuntimeError("CPU not supported")
-        P = P.contiguous()
-        if V.stride(3) != 1 or any(s % 4 for s in V.stride()[:3]) or V.data_ptr() % 16:
-            V = V.contiguous()
-        B, H, K, D = V.shape
-        with torch.cuda.device(P.device):
-            R = torch.empty(B, K, K, H * D, dtype=torch.float32, device=P.device)
-            check(lib.spacap_relation_feature_fwd_f32(P.data_ptr(), V.data_ptr(), V.stride(0), V.stride(1), V.stride(2),
-                                                      B, H, K, D, R.data_ptr(),
-                                                      torch.cuda.current_stream(P.device).cuda_stream),
-                  "spacap_relation_feature_fwd_f32")
-        ctx.save_for_backward(P, V)
-        return R
-
-    @staticmethod
-    def backward(ctx, dR):
-        P, V = ctx.saved_tensors
-        B, H, K, D = V.shape
-        dR = dR.contiguous()
-        with torch.cuda.device(P.device):
-            dP = torch.empty_like(P)
-            dV = torch.empty(B, K, H, D, dtype=torch.float32, device=P.device)
-            check(lib.spacap_relation_feature_bwd_f32(dR.data_ptr(), P.data_ptr(), V.data_ptr(), V.stride(0), V.stride(1),
-                                                      V.stride(2), B, H, K, D, dP.data_ptr(), dV.data_ptr(),
-                                                      torch.cuda.current_stream(P.device).cuda_stream),
-                  "spacap_relation_feature_bwd_f32")
-        return dP, dV.transpose(1, 2)
-
-
-def relation_feature(P, V):
-    return RelationFeature.apply(P, V)
-
-
-class RelationLayer1(Function):
-    """relu(b1 + sum_h P[b,h,i,j] * U[b,j,h,:])  -- see csrc/relation.hip."""
-
-    @staticmethod
-    def forward(ctx, P, U, b1):
-        P, U = P.contiguous(), U.contiguous()
-        B, H, K, _ = P.shape
-        C = U.shape[-1]
-        with torch.cuda.device(P.device):
-            H1 = torch.empty(B, K, K, C, dtype=torch.float32, device=P.device)
-            check(lib.spacap_relation_l1_fwd_f32(P.data_ptr(), U.data_ptr(), b1.data_ptr(), B, H, K, C, H1.data_ptr(),
-                                                 torch.cuda.current_stream(P.device).cuda_stream), "spacap_relation_l1_fwd_f32")
-        ctx.save_for_backward(P, U, H1)
-        return H1
-
-    @staticmethod
-    def backward(ctx, dH1):
-        P, U, H1 = ctx.saved_tensors
-        B, H, K, _ = P.shape
-        C = U.shape[-1]
-        dH1 = dH1.contiguous()
-        with torch.cuda.device(P.device):
-            dP = torch.empty_like(P)
-            dU = torch.empty(int(lib.spacap_relation_l1_isplit()), *U.shape, dtype=torch.float32, device=P.device)
-            part = torch.empty(int(lib.spacap_relation_l1_blocks(B, K, C)), C, dtype=torch.float32, device=P.device)
-            check(lib.spacap_relation_l1_bwd_f32(dH1.data_ptr(), H1.data_ptr(), P.data_ptr(), U.data_ptr(), B, H, K, C,
-                                                 dP.data_ptr(), dU.data_ptr(), part.data_ptr(),
-                                                 torch.cuda.current_stream(P.device).cuda_stream), "spacap_relation_l1_bwd_f32")
-        return dP, sum_slabs(dU), sum_slabs(part)
-
-
-def relation_layer1(P, V, weight, bias):
-    """First Linear + ReLU of the relation MLP applied to the relation feature of (P, V), without forming the feature:
-    P (B,h,K,K), V (B,h,K,d) (any strides), weight (C, h*d), bias (C) -> (B,K,K,C)."""
-    if not P.is_cuda:
-        raise RuntimeError("CPU not supported")
-    B, H, K, D = V.shape
-    C = weight.shape[0]
-    if not lib.spacap_relation_l1_supported(H, K, C):
-        # widths without a fused kernel (cfg5: d_model 512): the feature is formed (one launch) and multiplied by BLAS
-        return torch.relu(torch.nn.functional.linear(RelationFeature.apply(P, V), weight, bias))
-    U = torch.einsum("bhjd,ohd->bjho", V, weight.view(C, H, D))  # (B,K,H,C): tiny, autograd gives dV and dW1
-    return RelationLayer1.apply(P, U, bias)
+def __getattr__(name):
+    """The relation feature and first-layer nodes moved to relation.py; their names stay importable from here."""
+    if name in ("RelationFeature", "RelationLayer1", "relation_feature", "relation_layer1"):
+        from . import relation
+        return getattr(relation, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

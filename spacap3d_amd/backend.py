@@ -27,8 +27,12 @@ class HipBackend:
         self.self_attention_packed = _att.self_attention_packed
         self.layer_norm = _att.layer_norm
         self.layer_norm_residual = _att.layer_norm_residual
-        self.relation_feature = _att.relation_feature
-        self.relation_layer1 = _att.relation_layer1
+        from . import relation as _rel
+        self.relation_feature = _rel.relation_feature
+        self.relation_layer1 = _rel.relation_layer1
+        self.relation_tail = _rel.relation_tail
+        self.relation_head = _rel.relation_head
+        self.relation_pred = _rel.relation_pred
         from . import fused_bn as _fbn
         self.bn_relu_train = _fbn.bn_relu_train
         self.bn_relu_eval = _fbn.bn_relu_eval
@@ -47,8 +51,6 @@ class HipBackend:
         self.linear = _lin.linear
         self.ffn_tail = _lin.ffn_tail
         self.conv1x1 = _lin.conv1x1
-        self.relation_tail = _lin.relation_tail
-        self.relation_head = _lin.relation_head
         self.vocab_projection = _lin.vocab_projection
         from . import caption_prep as _cp
         self.caption_prep = _cp.caption_prep

@@ -102,6 +102,23 @@ def _data_gradient(g2, weight):
     return g2 @ weight
 
 
+def _linear_grads(g2, x2, weight):
+    """(dW, db) of y = x W^T + b from g2 (R, CK), x2 (R, CP): the batched weight-gradient kernel + one slab sum into the
+    weight's gradient slot; plain products where the shape has no kernel (or off the device)."""
+    CK, CP = weight.shape
+    part = linear_wgrad_partials(g2.contiguous(), x2.contiguous(), True, deferrable=True) if g2.is_cuda else None
+    if part is None:
+        return g2.t() @ x2, g2.sum(0)
+    s = sum_slabs(part, deferrable=True, out=grad_slot(weight, CK * CP + CK))
+    return s[:CK * CP].view(CK, CP), s[CK * CP:]
+
+
+def _route_qkv(dw, db, rows):
+    """gradients of the packed (3 d, d) weight / (3 d) bias as slices for the three nn.Linear parameters."""
+    a, b = rows[0], rows[0] + rows[1]
+    return (dw[:a], dw[a:b], dw[b:], db[:a], db[a:b], db[b:])
+
+
 class FusedLinear(Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -113,14 +130,8 @@ class FusedLinear(Function):
         x, weight = ctx.saved_tensors
         CK, CP = weight.shape
         g2 = g.reshape(-1, CK)
-        x2 = x.reshape(-1, CP)
-        R = g2.shape[0]
         dx = _data_gradient(g2, weight).view_as(x) if ctx.needs_input_grad[0] else None
-        part = linear_wgrad_partials(g2.contiguous(), x2.contiguous(), True, deferrable=True) if g2.is_cuda else None
-        if part is None:
-            return dx, g2.t() @ x2, g2.sum(0)
-        s = sum_slabs(part, deferrable=True, out=grad_slot(weight, CK * CP + CK))
-        return dx, s[:CK * CP].view(CK, CP), s[CK * CP:]
+        return (dx,) + _linear_grads(g2, x.reshape(-1, CP), weight)
 
 
 def linear(x, weight, bias):
@@ -162,12 +173,7 @@ class FFNTail(Function):
             dh = torch.empty_like(y2)
             check(lib.spacap_linear_dgrad_mask_f32(g2.data_ptr(), weight.contiguous().data_ptr(), y2.data_ptr(), scale, R, CK,
                                                    CP, dh.data_ptr(), st), "spacap_linear_dgrad_mask_f32")
-            part = linear_wgrad_partials(g2, y2.contiguous(), True, deferrable=True)
-            if part is None:
-                dw, db = g2.t() @ y2, g2.sum(0)
-            else:
-                s = sum_slabs(part, deferrable=True, out=grad_slot(weight, CK * CP + CK))
-                dw, db = s[:CK * CP].view(CK, CP), s[CK * CP:]
+            dw, db = _linear_grads(g2, y2, weight)
         return dh.view_as(y), dw, db, None, None
 
 
@@ -199,16 +205,8 @@ class PackedLinear(Function):
         CK, CP = weight.shape
         g2 = g.reshape(-1, CK).contiguous()
         x2 = x.reshape(-1, CP).contiguous()
-        R = g2.shape[0]
         dx = _data_gradient(g2, weight).view_as(x) if ctx.needs_input_grad[0] else None
-        part = linear_wgrad_partials(g2, x2, True, deferrable=True)
-        if part is None:
-            dw, db = g2.t() @ x2, g2.sum(0)
-        else:
-            s = sum_slabs(part, deferrable=True, out=grad_slot(weight, CK * CP + CK))
-            dw, db = s[:CK * CP].view(CK, CP), s[CK * CP:]
-        a, b, _ = ctx.split
-        return (dx, None, None, dw[:a], dw[a:a + b], dw[a + b:], db[:a], db[a:a + b], db[a + b:])
+        return (dx, None, None) + _route_qkv(*_linear_grads(g2, x2, weight), ctx.split)
 
 
 def packed_views(flat, params_w, params_b):
@@ -318,220 +316,6 @@ def conv1x1(x, conv):
     return Conv1x1.apply(x, conv.weight, conv.bias)
 
 
-class RelationTail(Function):
-    """pred = W3 relu(W2 hid1 + b2) + b3 on the B*K*K pair rows of the relation head
-    (models/transformer_captioner.py:319-326, 392-397; hid1 = the first layer's ReLU output, 524 288 x 128 at the
-    benchmark shape).  Forward: ONE kernel reads hid1 and writes hid2 and pred (csrc/sa_fwd.hip: sa_mid_fwd_kernel, TAIL).
-    Backward: one streaming kernel gives dz2 = (dpred W3) * (hid2 > 0) and the partial sums of dW3, db2, db3
-    (csrc/rel_tail.hip: rel_tail_bwd_kernel); dhid1 = dz2 W2 and dW2 = dz2^T hid1 are MFMA-bound BLAS GEMMs (the latter cut into 64 row
-    slabs: the BLAS heuristics do not split that reduction)."""
-
-    SLABS = 64
-
-    @staticmethod
-    def forward(ctx, hid1, W2, b2, W3, b3):
-        shape = hid1.shape
-        h1 = hid1.reshape(-1, 128).contiguous()
-        R = h1.shape[0]
-        dev = h1.device
-        W2c, W3c = W2.contiguous(), W3.contiguous()
-        with torch.cuda.device(dev):
-            hid2 = torch.empty_like(h1)
-            pred = torch.empty(R, W3.shape[0], dtype=torch.float32, device=dev)
-            check(lib.spacap_rel_tail_fwd_f32(h1.data_ptr(), W2c.data_ptr(), b2.data_ptr(), W3c.data_ptr(), b3.data_ptr(), R,
-                                              hid2.data_ptr(), pred.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                  "spacap_rel_tail_fwd_f32")
-        ctx.save_for_backward(h1, hid2, W2c, W3c)
-        ctx.shape = shape
-        return pred.view(*shape[:-1], W3.shape[0])
-
-    @staticmethod
-    def backward(ctx, g):
-        h1, hid2, W2, W3 = ctx.saved_tensors
-        NO = W3.shape[0]
-        g2 = g.reshape(-1, NO).contiguous()
-        R = g2.shape[0]
-        dev = g2.device
-        with torch.cuda.device(dev):
-            nparts = int(lib.spacap_rel_tail_bwd_nparts(R))
-            PW = NO * 128 + 128 + 16
-            part = torch.empty(nparts, PW, dtype=torch.float32, device=dev)
-            dz2 = torch.empty_like(hid2)
-            check(lib.spacap_rel_tail_bwd_f32(g2.data_ptr(), W3.data_ptr(), hid2.data_ptr(), R, dz2.data_ptr(), part.data_ptr(),
-                                              torch.cuda.current_stream(dev).cuda_stream), "spacap_rel_tail_bwd_f32")
-            s = sum_slabs(part, deferrable=True)
-            dW3, db2, db3 = s[:NO * 128].view(NO, 128), s[NO * 128:NO * 128 + 128], s[NO * 128 + 128:NO * 128 + 128 + NO]
-            dh1 = None
-            if ctx.needs_input_grad[0]:
-                if R >= 49152 and lib.spacap_gemm_rows_supported(128, 128):
-                    # dz2 W2 on the streaming split-bf16 kernel (fp32-equivalent; 170 us in BLAS -> ~125 us at 524 288 rows)
-                    dh1 = torch.empty_like(hid2)
-                    W2t = W2.t().contiguous()
-                    check(lib.spacap_gemm_rows_f32(dz2.data_ptr(), W2t.data_ptr(), R, 128, 128, dh1.data_ptr(),
-                                                   torch.cuda.current_stream(dev).cuda_stream), "spacap_gemm_rows_f32")
-                    dh1 = dh1.view(ctx.shape)
-                else:
-                    dh1 = (dz2 @ W2).view(ctx.shape)
-            S = RelationTail.SLABS
-            if R % S == 0 and R >= 64 * S:
-                dW2 = sum_slabs(torch.bmm(dz2.view(S, R // S, 128).transpose(1, 2), h1.view(S, R // S, 128)).view(S, -1),
-                                deferrable=True).view(128, 128)
-            else:
-                dW2 = dz2.t() @ h1
-        return dh1, dW2, db2, dW3, db3
-
-
-def relation_tail(hid1, lin2, lin3):
-    """``lin3(relu(lin2(hid1)))`` for the relation head's 128 -> 128 -> 9 tail; ``None`` for other shapes."""
-    if not hid1.is_cuda or hid1.dtype != torch.float32 or tuple(lin2.weight.shape) != (128, 128) or \
-            tuple(lin3.weight.shape) != (9, 128) or lin2.bias is None or lin3.bias is None or hid1.shape[-1] != 128:
-        return None
-    return RelationTail.apply(hid1, lin2.weight, lin2.bias, lin3.weight, lin3.bias)
-
-
-class RelationHead(Function):
-    """The whole relation head (models/transformer_captioner.py:319-326, 392-397) as one kernel each way
-    (csrc/relation_fused.hip): pred = W3 relu(W2 relu(b1 + sum_h P U) + b2) + b3 on the B*K*K pairs, with
-    U[b,j,h,:] = V[b,h,j,:] W1[:, 16h:16h+16]^T formed by the caller.  Neither the pair feature nor the first hidden layer
-    nor any gradient of pair size exists in HBM: the forward stores hid2 (the backward's one large input) and pred; the
-    backward returns dP, the dU partials and per-workgroup partial sums of dW2, dW3, db1, db2, db3.  It visits only the
-    (query row) x (key column) sub-grid on which the incoming gradient is not zero (found on the device from the gradient
-    itself: the relation loss weights pair (i, j) by "both proposals selected")."""
-
-    @staticmethod
-    def forward(ctx, P, U, b1, W2, b2, W3, b3):
-        P, U, W2c, W3c = P.contiguous(), U.contiguous(), W2.contiguous(), W3.contiguous()
-        B, H, K, _ = P.shape
-        dev = P.device
-        with torch.cuda.device(dev):
-            hid2 = torch.empty(B, K, K, 128, dtype=torch.float32, device=dev)
-            pred = torch.empty(B, K, K, 9, dtype=torch.float32, device=dev)
-            check(lib.spacap_relation_fused_fwd_f32(P.data_ptr(), U.data_ptr(), b1.data_ptr(), W2c.data_ptr(), b2.data_ptr(),
-                                                    W3c.data_ptr(), b3.data_ptr(), B, K, hid2.data_ptr(), pred.data_ptr(),
-                                                    torch.cuda.current_stream(dev).cuda_stream), "spacap_relation_fused_fwd_f32")
-        ctx.save_for_backward(P, U, b1, W2c, W3c, hid2)
-        return pred
-
-    @staticmethod
-    def backward(ctx, g):
-        P, U, b1, W2, W3, hid2 = ctx.saved_tensors
-        B, H, K, _ = P.shape
-        dev = P.device
-        g = g.contiguous()
-        with torch.cuda.device(dev):
-            PW = int(lib.spacap_relation_fused_part_floats())
-            nparts = int(lib.spacap_relation_fused_nparts(B, K))
-            zslots = int(lib.spacap_relation_fused_sel_zsplit(B, K, nparts))
-            part = torch.empty(nparts, PW, dtype=torch.float32, device=dev)
-            dP = torch.empty_like(P)
-            dU = torch.empty(zslots, *U.shape, dtype=torch.float32, device=dev)
-            ws = torch.empty(int(lib.spacap_relation_fused_sel_workspace_bytes(B, K)), dtype=torch.uint8, device=dev)
-            check(lib.spacap_relation_fused_bwd_sel_f32(g.data_ptr(), hid2.data_ptr(), P.data_ptr(), U.data_ptr(), b1.data_ptr(),
-                                                        W2.data_ptr(), W3.data_ptr(), B, K, nparts, zslots, dP.data_ptr(),
-                                                        dU.data_ptr(), part.data_ptr(), ws.data_ptr(),
-                                                        torch.cuda.current_stream(dev).cuda_stream),
-                  "spacap_relation_fused_bwd_sel_f32")
-            s = sum_slabs(part, deferrable=True)
-        o = 128 * 128
-        dW2, dW3 = s[:o].view(128, 128), s[o:o + 9 * 128].view(9, 128)
-        o += 9 * 128
-        return dP, sum_slabs(dU), s[o:o + 128], dW2, s[o + 128:o + 256], dW3, s[o + 256:o + 265]
-
-
-class RelationWide(Function):
-    """The relation head at widths the one-kernel form has no kernel for (the 512-wide / 32-head stress configuration;
-    models/transformer_captioner.py:319-326, 392-397 at d_model = 512), composed of this library's kernels:
-        hid1 = relu(b1 + sum_h P U)            csrc/gemm_bf3.hip: rel_wide_l1_* (the pair feature is never formed: U = per-head first
-                                               Linear of V; one workgroup per key column on the matrix cores, P read transposed)
-        hid2 = relu(hid1 W2^T + b2)            csrc/gemm_bf3.hip (tiled split-bf16 product, bias + ReLU in its epilogue)
-        pred = hid2 W3^T + b3                  csrc/dense_rows.hip
-    backward: dz2 / dW3 / db2 / db3 in one pass over hid2 (rel_wide_tail_bwd_kernel), dW2 = dz2^T hid1 and dhid1 = dz2 W2 as
-    split-bf16 products, then the first layer's backward (masks by hid1 > 0 itself).  Three tensors of pair size live between
-    forward and backward (hid1, hid2; dz2 in the backward; dhid1 reuses hid2's memory)."""
-
-    @staticmethod
-    def forward(ctx, P, U, b1, W2, b2, W3, b3):
-        P, U, W2c, W3c = P.contiguous(), U.contiguous(), W2.contiguous(), W3.contiguous()
-        B, H, K, _ = P.shape
-        C = U.shape[-1]
-        dev = P.device
-        st = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            Pt = torch.empty(B, K, H, K, dtype=torch.float32, device=dev)      # Pt[b,j,h,i] = P[b,h,i,j]: a key column's block contiguous
-            check(lib.spacap_rel_wide_transpose_f32(P.data_ptr(), Pt.data_ptr(), B, H, K, 1, st), "spacap_rel_wide_transpose_f32")
-            hid1 = torch.empty(B * K * K, C, dtype=torch.float32, device=dev)
-            check(lib.spacap_rel_wide_l1_fwd_f32(Pt.data_ptr(), U.data_ptr(), b1.data_ptr(), B, H, K, C, hid1.data_ptr(), st),
-                  "spacap_rel_wide_l1_fwd_f32")
-            hid2 = bf3_product(hid1, bf3_pieces(W2c), b2, relu=True)
-            pred = dense_product(hid2, W3c, True, bias=b3)
-        ctx.save_for_backward(Pt, U, W2c, W3c, hid1, hid2)
-        ctx.spent = False
-        return pred.view(B, K, K, W3c.shape[0])
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.spent:    # (dhid1 is written into hid2's memory: a second backward over a retained graph would read garbage)
-            raise RuntimeError("RelationWide: its backward can run once per forward (retain_graph is not supported)")
-        ctx.spent = True
-        Pt, U, W2, W3, hid1, hid2 = ctx.saved_tensors
-        B, K, H, _ = Pt.shape
-        C = U.shape[-1]
-        NO = W3.shape[0]
-        R = B * K * K
-        dev = Pt.device
-        st = torch.cuda.current_stream(dev).cuda_stream
-        g2 = g.reshape(R, NO).contiguous()
-        with torch.cuda.device(dev):
-            nparts = int(lib.spacap_rel_wide_tail_nparts(R))
-            part = torch.empty(nparts, NO * C + C + 16, dtype=torch.float32, device=dev)
-            dz2 = torch.empty_like(hid2)
-            check(lib.spacap_rel_wide_tail_bwd_f32(g2.data_ptr(), W3.data_ptr(), hid2.data_ptr(), R, C, nparts, dz2.data_ptr(),
-                                                   part.data_ptr(), st), "spacap_rel_wide_tail_bwd_f32")
-            s = sum_slabs(part, deferrable=True)
-            dW3, db2, db3 = s[:NO * C].view(NO, C), s[NO * C:NO * C + C], s[NO * C + C:NO * C + C + NO]
-            nslab = int(lib.spacap_gemm_bf3_wgrad_slabs(R, C, C))
-            pw = torch.empty(nslab, C * C, dtype=torch.float32, device=dev)
-            # the Linear layers' split-bf16 weight-gradient kernel (row-major images read by transposing LDS reads:
-            # csrc/linear_grad.hip)
-            check(lib.spacap_linear_wgrad_nslab_f32(dz2.data_ptr(), hid1.data_ptr(), R, C, C, 0, nslab, pw.data_ptr(), st),
-                  "spacap_linear_wgrad_nslab_f32")
-            dW2 = sum_slabs(pw, deferrable=True).view(C, C)
-            dh1 = bf3_product(dz2, bf3_pieces(W2, trans=True), out=hid2)      # hid2 is dead: its memory takes dhid1
-            del dz2
-            dPt, dU = torch.empty_like(Pt), torch.empty_like(U)
-            pb = torch.empty(B * K, C, dtype=torch.float32, device=dev)
-            check(lib.spacap_rel_wide_l1_bwd_f32(dh1.data_ptr(), hid1.data_ptr(), Pt.data_ptr(), U.data_ptr(), B, H, K, C, dPt.data_ptr(),
-                                                 dU.data_ptr(), pb.data_ptr(), st), "spacap_rel_wide_l1_bwd_f32")
-            dP = torch.empty(B, H, K, K, dtype=torch.float32, device=dev)
-            check(lib.spacap_rel_wide_transpose_f32(dPt.data_ptr(), dP.data_ptr(), B, H, K, 0, st), "spacap_rel_wide_transpose_f32")
-        return dP, dU, sum_slabs(pb), dW2, db2, dW3, db3
-
-
-def relation_head_wide(P, V, lin1, lin2, lin3):
-    """``relation_head`` for widths without the one-kernel form; ``None`` when these kernels do not cover the shape either."""
-    B, H, K, D = V.shape
-    C = lin1.weight.shape[0]
-    if not P.is_cuda or P.dtype != torch.float32 or lin1.bias is None or lin2.bias is None or lin3.bias is None or \
-            tuple(lin1.weight.shape) != (C, H * D) or tuple(lin2.weight.shape) != (C, C) or lin3.weight.shape[1] != C or \
-            lin3.weight.shape[0] != 9 or not lib.spacap_rel_wide_l1_supported(H, K, C) or \
-            not lib.spacap_gemm_bf3_supported(C, C) or not lib.spacap_rel_wide_tail_supported(C):
-        return None
-    U = RelationU.apply(V, lin1.weight)
-    return RelationWide.apply(P, U, lin1.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias)
-
-
-def relation_head(P, V, lin1, lin2, lin3):
-    """``lin3(relu(lin2(relu(lin1(feature(P, V))))))`` -> (B,K,K,9) through ``RelationHead``; ``None`` when the shape has
-    no fused kernel (the caller composes relation_layer1 / relation_tail instead).  P (B,h,K,K), V (B,h,K,d)."""
-    B, H, K, D = V.shape
-    if not P.is_cuda or P.dtype != torch.float32 or lin1.bias is None or lin2.bias is None or lin3.bias is None or \
-            tuple(lin1.weight.shape) != (128, H * D) or tuple(lin2.weight.shape) != (128, 128) or \
-            not lib.spacap_relation_fused_supported(H, K, 128, lin3.weight.shape[0]) or lin3.weight.shape[1] != 128:
-        return relation_head_wide(P, V, lin1, lin2, lin3) if torch.is_grad_enabled() or P.is_cuda else None
-    U = RelationU.apply(V, lin1.weight)   # (B,K,H,C): the first Linear applied per head to the value vectors
-    return RelationHead.apply(P, U, lin1.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias)
-
-
 # ---- dense row products of any shape (csrc/dense_rows.hip): what used to be rocBLAS GEMMs inside the step ----------------------
 
 def _dense(dev, a_ptr, lda, W_ptr, ldw, trans_w, bias_ptr, R, K, CO, out_ptr, ldo, a_rows=(0, 0, 0), o_rows=(0, 0, 0), o_zero=0,
@@ -625,49 +409,9 @@ def vocab_projection(n, lin, skip):
     return VocabProjection.apply(n, lin.weight, lin.bias, skip)
 
 
-class RelationU(Function):
-    """U[b, j, h, :] = W1[:, d h : d h + d] V[b, h, j, :]: the relation head's first Linear applied per head to the value vectors
-    (models/transformer_captioner.py:319-326 with the pair feature of :393-397 factored, see relation_head).  V is the (B, h, K, d)
-    VIEW of the packed q | k | v projection (row stride 3 h d): read in place.  h independent products of one launch each way;
-    the weight gradient is h diagonal blocks of dU^T V (per-slab partials in dW1's own layout + one deferrable sum)."""
-
-    @staticmethod
-    def forward(ctx, V, W1):
-        B, H, K, D = V.shape
-        C = W1.shape[0]
-        Vr = V.transpose(1, 2)                      # (B, K, H, D)
-        if not (Vr.stride(3) == 1 and Vr.stride(2) == D and Vr.stride(0) == K * Vr.stride(1)):
-            Vr = Vr.contiguous()
-        W1c = W1.contiguous()
-        lda = Vr.stride(1)
-        dev = V.device
-        with torch.cuda.device(dev):
-            U = torch.empty(B, K, H, C, dtype=torch.float32, device=dev)
-            _dense(dev, Vr.data_ptr(), lda, W1c.data_ptr(), H * D, True, None, B * K, D, C, U.data_ptr(), H * C, slices=H,
-                   slice_stride=C, batch=1, a_z=D, w_z=D)
-        ctx.save_for_backward(Vr, W1c)
-        return U
-
-    @staticmethod
-    def backward(ctx, dU):
-        Vr, W1 = ctx.saved_tensors
-        B, K, H, D = Vr.shape
-        C = W1.shape[0]
-        R = B * K
-        dev = dU.device
-        dU = dU.contiguous()
-        lda = Vr.stride(1)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            dV = None
-            if ctx.needs_input_grad[0]:
-                dVr = torch.empty(B, K, H, D, dtype=torch.float32, device=dev)
-                _dense(dev, dU.data_ptr(), H * C, W1.data_ptr(), H * D, False, None, R, C, D, dVr.data_ptr(), H * D, slices=H,
-                       slice_stride=D, batch=1, a_z=C, w_z=D)
-                dV = dVr.transpose(1, 2)
-            nslab = int(lib.spacap_dense_wgrad_blocks_slabs(R))
-            part = torch.empty(nslab, C * H * D, dtype=torch.float32, device=dev)
-            check(lib.spacap_dense_wgrad_blocks_f32(dU.data_ptr(), H * C, Vr.data_ptr(), lda, R, H, C, D, nslab, part.data_ptr(), st),
-                  "spacap_dense_wgrad_blocks_f32")
-            dW1 = sum_slabs(part, deferrable=True).view(C, H * D)
-        return dV, dW1
+def __getattr__(name):
+    """The relation head's nodes moved to relation.py (which imports this module); their names stay importable from here."""
+    if name in ("RelationTail", "RelationHead", "RelationWide", "RelationU", "relation_tail", "relation_head_wide", "relation_head"):
+        from . import relation
+        return getattr(relation, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -18,7 +18,9 @@ import ctypes
 import torch
 from torch.autograd import Function
 
-from ._native import TfRowsArgs, check, grad_slot, lib, linear_wgrad_partials, sum_slabs
+from ._native import TfRowsArgs, check, lib, sum_slabs
+from .attention import Operands, _next_seed, _prep_mask, mha_backward_delta, mha_forward, rng_state, self_attention_packed
+from .linear import _linear_grads, _route_qkv
 
 D_MODEL = 128
 # tests switch the fused stacks off here (the per-operator path of transformer_captioner.py then runs)
@@ -46,7 +48,6 @@ def _rows(mode, R, dev, **kw):
     a.seed = int(kw.pop("seed", 0))
     a.seed_dev = None
     if a.drop_p > 0.0:
-        from .attention import rng_state
         a.seed_dev = rng_state(dev).data_ptr()
     for k, v in kw.items():
         setattr(a, k, _p(v))
@@ -77,22 +78,6 @@ def _split_product(a2, W, trans_w):
 def _ln_param_grads(part):
     s = sum_slabs(part, deferrable=True)
     return s[:D_MODEL], s[D_MODEL:]
-
-
-def _linear_grads(g2, x2, weight):
-    """(dW, db) of y = x W^T + b from g2 (R, CK), x2 (R, CP): the batched weight-gradient kernel + one slab sum."""
-    CK, CP = g2.shape[1], x2.shape[1]
-    part = linear_wgrad_partials(g2, x2, True, deferrable=True)
-    if part is None:
-        return g2.t() @ x2, g2.sum(0)
-    s = sum_slabs(part, deferrable=True, out=grad_slot(weight, CK * CP + CK))
-    return s[:CK * CP].view(CK, CP), s[CK * CP:]
-
-
-def _route_qkv(dw, db, rows):
-    """gradients of the packed (3 d, d) weight / (3 d) bias as slices for the three nn.Linear parameters."""
-    a, b = rows[0], rows[0] + rows[1]
-    return (dw[:a], dw[a:b], dw[b:], db[:a], db[a:b], db[b:])
 
 
 class LnQkv(Function):
@@ -149,7 +134,6 @@ _FFN_PIECES = {}      # w_1.weight.data_ptr() -> (weakref to that parameter, bf1
 def refresh_ffn_pieces(layers):
     """One launch: the four split-bf16 images (W1, W2, W2^T, W1^T) of every layer's feed-forward weights, into a buffer that
     lives with the stack (so a captured hipGraph replays the launch on the same memory)."""
-    import ctypes
     import weakref
     ffs = [l.feed_forward for l in layers]
     if not ffs or not FFN_BF3:
@@ -178,7 +162,6 @@ def refresh_ffn_pieces(layers):
 
 def _ffn(mode, x2, Wa, Wb, bias, y, dff, p, seed, dev):
     """One launch of the chained feed-forward kernel: (hid (R, dff), parts (dff / 128, R, 128))."""
-    from .attention import rng_state
     R = x2.shape[0]
     hid, parts = _new(dev, R, dff), _new(dev, dff // 128, R, D_MODEL)
     st = torch.cuda.current_stream(dev).cuda_stream
@@ -194,6 +177,44 @@ def _ffn(mode, x2, Wa, Wb, bias, y, dff, p, seed, dev):
     return hid, parts
 
 
+def _out_ffn1_forward(a, xr, Wo, bo, ln_a, ln_b, W1, b1, W2, eps, p_sub, p_ffn, seed1, seed2):
+    """x1 = xr + dropout(a Wo^T + bo), n2 = LayerNorm(x1) (one row launch); h, parts of the feed-forward's first half (one launch):
+    (x1, n2, stats, h, parts)."""
+    R, dev = xr.numel() // D_MODEL, xr.device
+    with torch.cuda.device(dev):
+        x1, n2, stats = _new(dev, *xr.shape), _new(dev, R, D_MODEL), _new(dev, R, 2)
+        _rows(0, R, dev, a1=a, w1=Wo, bias1=bo, k1=D_MODEL, drop_p=p_sub, seed=seed1, res=xr, x_out=x1, ln_a=ln_a,
+              ln_b=ln_b, eps=eps, n_out=n2, stats=stats)
+        h, parts = _ffn(0, n2, W1, W2, b1, None, W1.shape[0], p_ffn, seed2, dev)
+    return x1, n2, stats, h.view(*xr.shape[:-1], W1.shape[0]), parts
+
+
+def _out_ffn1_backward(a, x1, n2, stats, ln_a, Wo, W1, eps, p_sub, seed1, g_x1, g_hpre, g_parts, **attn):
+    """(da, dx1, dWo, dbo, dln_a, dln_b, dW1, db1) of ``_out_ffn1_forward`` in one row launch (+ the queued parameter gradients);
+    ``attn`` = the keywords with which the row kernel also emits the attention backward's row term (AttnFfn1)."""
+    R, dev = x1.numel() // D_MODEL, x1.device
+    dff = W1.shape[0]
+    with torch.cuda.device(dev):
+        dx1, dy1, da, part = _new(dev, *x1.shape), _new(dev, R, D_MODEL), _new(dev, *a.shape), _parts(dev, R)
+        kw = dict(x_ln=x1, stats=stats, ln_a=ln_a, eps=eps, res=g_x1.contiguous() if g_x1 is not None else None,
+                  x_out=dx1, part=part, drop_p=p_sub, seed=seed1, n_out=dy1, w2=Wo, n2=D_MODEL, out2=da, **attn)
+        dW1 = db1 = None
+        if g_hpre is not None:
+            gh = g_hpre.reshape(R, dff).contiguous()
+            if g_parts is not None:
+                gp = g_parts.contiguous()
+                _rows(1, R, dev, a1=gp, nparts=gp.shape[0], **kw)
+            else:
+                parts, S = _split_product(gh, W1, False)
+                _rows(1, R, dev, a1=parts, nparts=S, **kw)
+            dW1, db1 = _linear_grads(gh, n2, W1)
+        else:   # the hidden layer was not used downstream: only the residual path carries a gradient
+            _rows(1, R, dev, g=torch.zeros(R, D_MODEL, dtype=torch.float32, device=dev), **kw)
+        dln_a, dln_b = _ln_param_grads(part)
+        dWo, dbo = _linear_grads(dy1, a.reshape(R, D_MODEL), Wo)
+    return da, dx1, dWo, dbo, dln_a, dln_b, dW1, db1
+
+
 class AttnOutFfn1(Function):
     """(x1, h, parts):  x1 = x + dropout(a Wo^T + bo);  h = dropout(relu(LayerNorm(x1) W1^T + b1));  parts = the partial sums
     of h W2^T over the 128-wide slices of d_ff (same launch as h: the hidden tile never leaves the chip between the two
@@ -205,43 +226,15 @@ class AttnOutFfn1(Function):
         if not a.is_cuda:
             raise RuntimeError("CPU not supported")
         ac, xr = a.contiguous(), xres.contiguous()
-        R, dev = xr.numel() // D_MODEL, xr.device
-        dff = W1.shape[0]
-        with torch.cuda.device(dev):
-            x1, n2, stats = _new(dev, *xr.shape), _new(dev, R, D_MODEL), _new(dev, R, 2)
-            _rows(0, R, dev, a1=ac, w1=Wo, bias1=bo, k1=D_MODEL, drop_p=p_sub, seed=seed1, res=xr, x_out=x1, ln_a=ln_a,
-                  ln_b=ln_b, eps=eps, n_out=n2, stats=stats)
-            h, parts = _ffn(0, n2, W1, W2, b1, None, dff, p_ffn, seed2, dev)
+        x1, n2, stats, h, parts = _out_ffn1_forward(ac, xr, Wo, bo, ln_a, ln_b, W1, b1, W2, eps, p_sub, p_ffn, seed1, seed2)
         ctx.save_for_backward(ac, x1, n2, stats, ln_a, Wo, W1)
         ctx.meta = (float(eps), float(p_sub), int(seed1))
         ctx.set_materialize_grads(False)
-        return x1, h.view(*xr.shape[:-1], dff), parts
+        return x1, h, parts
 
     @staticmethod
-    def backward(ctx, g_x1, g_hpre, g_parts):
-        ac, x1, n2, stats, ln_a, Wo, W1 = ctx.saved_tensors
-        eps, p_sub, seed1 = ctx.meta
-        R, dev = x1.numel() // D_MODEL, x1.device
-        dff = W1.shape[0]
-        with torch.cuda.device(dev):
-            dx1, dy1, da, part = _new(dev, *x1.shape), _new(dev, R, D_MODEL), _new(dev, *ac.shape), _parts(dev, R)
-            kw = dict(x_ln=x1, stats=stats, ln_a=ln_a, eps=eps, res=g_x1.contiguous() if g_x1 is not None else None,
-                      x_out=dx1, part=part, drop_p=p_sub, seed=seed1, n_out=dy1, w2=Wo, n2=D_MODEL, out2=da)
-            dW1 = db1 = None
-            if g_hpre is not None:
-                gh = g_hpre.reshape(R, dff).contiguous()
-                if g_parts is not None:
-                    gp = g_parts.contiguous()
-                    _rows(1, R, dev, a1=gp, nparts=gp.shape[0], **kw)
-                else:
-                    parts, S = _split_product(gh, W1, False)
-                    _rows(1, R, dev, a1=parts, nparts=S, **kw)
-                dW1, db1 = _linear_grads(gh, n2, W1)
-            else:   # the hidden layer was not used downstream: only the residual path carries a gradient
-                _rows(1, R, dev, g=torch.zeros(R, D_MODEL, dtype=torch.float32, device=dev), **kw)
-            dln_a, dln_b = _ln_param_grads(part)
-            dWo, dbo = _linear_grads(dy1, ac.reshape(R, D_MODEL), Wo)
-        return da, dx1, dWo, dbo, dln_a, dln_b, dW1, db1, None, None, None, None, None, None
+    def backward(ctx, *grads):
+        return _out_ffn1_backward(*ctx.saved_tensors, *ctx.meta, *grads) + (None,) * 6
 
 
 class AttnFfn1(Function):
@@ -256,75 +249,25 @@ class AttnFfn1(Function):
                 p_ffn, seed1, seed2):
         if not qkv.is_cuda:
             raise RuntimeError("CPU not supported")
-        import math
-        from .attention import mha_args
         qc, xr = qkv.contiguous(), xres.contiguous()
-        B, L, three = qc.shape
-        hd = three // 3
-        dk = hd // heads
-        R, dev = B * L, xr.device
-        dff = W1.shape[0]
-        es = qc.element_size()
-        strides = (L * three, dk, three)
-        scale = 1.0 / math.sqrt(dk)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            a, lse = _new(dev, B, L, hd), _new(dev, B, heads, L, 2)
-            base = qc.data_ptr()
-            check(lib.spacap_mha_fwd_f32(*mha_args(base, base + hd * es, base + 2 * hd * es, strides, strides, strides, mask_u8,
-                                                   mask_sb, mask_sq, None, B, heads, L, L, dk, scale, p_att, seed_att, dev),
-                                         a.data_ptr(), None, lse.data_ptr(), st), "spacap_mha_fwd_f32")
-            x1, n2, stats = _new(dev, *xr.shape), _new(dev, R, D_MODEL), _new(dev, R, 2)
-            _rows(0, R, dev, a1=a, w1=Wo, bias1=bo, k1=D_MODEL, drop_p=p_sub, seed=seed1, res=xr, x_out=x1, ln_a=ln_a,
-                  ln_b=ln_b, eps=eps, n_out=n2, stats=stats)
-            h, parts = _ffn(0, n2, W1, W2, b1, None, dff, p_ffn, seed2, dev)
-        ctx.save_for_backward(qc, mask_u8, lse, a, x1, n2, stats, ln_a, Wo, W1)
-        ctx.meta = (float(eps), float(p_sub), int(seed1), int(heads), mask_sb, mask_sq, float(p_att), int(seed_att), scale)
+        a, _, lse = mha_forward(Operands.packed(qc, heads), (mask_u8, mask_sb, mask_sq), None, p_att, seed_att, False)
+        a = a.view(qc.shape[0], qc.shape[1], -1)
+        x1, n2, stats, h, parts = _out_ffn1_forward(a, xr, Wo, bo, ln_a, ln_b, W1, b1, W2, eps, p_sub, p_ffn, seed1, seed2)
+        ctx.save_for_backward(a, x1, n2, stats, ln_a, Wo, W1, qc, mask_u8, lse)
+        ctx.meta = (float(eps), float(p_sub), int(seed1), int(heads), mask_sb, mask_sq, float(p_att), int(seed_att))
         ctx.set_materialize_grads(False)
-        return x1, h.view(*xr.shape[:-1], dff), parts
+        return x1, h, parts
 
     @staticmethod
-    def backward(ctx, g_x1, g_hpre, g_parts):
-        from .attention import mha_args
-        qc, mask_u8, lse, a, x1, n2, stats, ln_a, Wo, W1 = ctx.saved_tensors
-        eps, p_sub, seed1, heads, mask_sb, mask_sq, p_att, seed_att, scale = ctx.meta
-        B, L, three = qc.shape
-        hd = three // 3
-        dk = hd // heads
-        R, dev = B * L, x1.device
-        dff = W1.shape[0]
-        es = qc.element_size()
-        strides = (L * three, dk, three)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            dx1, dy1, da, part = _new(dev, *x1.shape), _new(dev, R, D_MODEL), _new(dev, B, L, hd), _parts(dev, R)
-            delta = _new(dev, B, heads, L)
-            kw = dict(x_ln=x1, stats=stats, ln_a=ln_a, eps=eps, res=g_x1.contiguous() if g_x1 is not None else None,
-                      x_out=dx1, part=part, drop_p=p_sub, seed=seed1, n_out=dy1, w2=Wo, n2=D_MODEL, out2=da, attn_out=a,
-                      delta_out=delta, lq=L)
-            dW1 = db1 = None
-            if g_hpre is not None and g_parts is not None:
-                gh, gp = g_hpre.reshape(R, dff).contiguous(), g_parts.contiguous()
-                _rows(1, R, dev, a1=gp, nparts=gp.shape[0], **kw)
-                dW1, db1 = _linear_grads(gh, n2, W1)
-            elif g_hpre is not None:
-                gh = g_hpre.reshape(R, dff).contiguous()
-                parts, S = _split_product(gh, W1, False)
-                _rows(1, R, dev, a1=parts, nparts=S, **kw)
-                dW1, db1 = _linear_grads(gh, n2, W1)
-            else:
-                _rows(1, R, dev, g=torch.zeros(R, D_MODEL, dtype=torch.float32, device=dev), **kw)
-            dln_a, dln_b = _ln_param_grads(part)
-            dWo, dbo = _linear_grads(dy1, a.reshape(R, D_MODEL), Wo)
-            dqkv = torch.empty_like(qc)
-            base, gb = qc.data_ptr(), dqkv.data_ptr()
-            # (the two halves of the attention gradient are independent once delta is known: one launch)
-            check(lib.spacap_mha_bwd_delta_f32(*mha_args(base, base + hd * es, base + 2 * hd * es, strides, strides, strides,
-                                                         mask_u8, mask_sb, mask_sq, None, B, heads, L, L, dk, scale, p_att,
-                                                         seed_att, dev),
-                                               lse.data_ptr(), da.data_ptr(), delta.data_ptr(), gb, gb + hd * es,
-                                               gb + 2 * hd * es, three, st), "spacap_mha_bwd_delta_f32")
-        return (dqkv, dx1, None, None, None, None, None, None, dWo, dbo, dln_a, dln_b, dW1, db1, None, None, None, None, None, None)
+    def backward(ctx, *grads):
+        *body, qc, mask_u8, lse = ctx.saved_tensors
+        *meta, heads, mask_sb, mask_sq, p_att, seed_att = ctx.meta
+        o = Operands.packed(qc, heads)
+        delta = _new(qc.device, o.B, heads, o.Lq)
+        da, *rest = _out_ffn1_backward(*body, *meta, *grads, attn_out=body[0], delta_out=delta, lq=o.Lq)
+        # (the two halves of the attention gradient are independent once delta is known: one launch)
+        (dqkv,) = mha_backward_delta(o, (mask_u8, mask_sb, mask_sq), p_att, seed_att, lse, da, delta)
+        return (dqkv, rest[0]) + (None,) * 6 + tuple(rest[1:]) + (None,) * 6
 
 
 class Ffn2Ln(Function):
@@ -422,8 +365,6 @@ def stack_supported(layers, x):
 def run_stack(layers, final_norm, x, mask):
     """The N pre-norm layers (self-attention + feed-forward each) followed by ``final_norm``
     (models/transformer_captioner.py: Encoder :166-178 / Decoder :193-207 in early-guide mode)."""
-    from .attention import _next_seed, _prep_mask, self_attention_packed
-
     def drop(m):
         return float(m.p) if m.training else 0.0
 

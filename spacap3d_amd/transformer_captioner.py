@@ -52,47 +52,6 @@ def _linear_wb(x, w, b):
     return f(x, w, b) if (f is not None and x.is_cuda) else F.linear(x, w, b)
 
 
-def _sum_slabs(t):
-    if not t.is_cuda:
-        return t.sum(0)
-    from ._native import sum_slabs
-    return sum_slabs(t.contiguous())
-
-
-class _TallLinear(torch.autograd.Function):
-    """y = x W^T + b for inputs with very many rows (the relation head runs its MLP on B*K*K = 524 288 pair
-    features).  Forward and dX are ordinary GEMMs; the weight gradient dW = G^T X reduces over all rows into a
-    128 x 128 output, which the BLAS heuristics run as a handful of tiles with no split over K (1.08 ms per
-    layer on MI355X); here the rows are cut into 64 slabs, multiplied as one batched GEMM and summed
-    (0.15 ms, fixed summation order)."""
-
-    SLABS = 64
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        ctx.save_for_backward(x, weight)
-        return F.linear(x, weight, bias)
-
-    @staticmethod
-    def backward(ctx, g):
-        x, weight = ctx.saved_tensors
-        g2 = g.reshape(-1, g.shape[-1])
-        x2 = x.reshape(-1, x.shape[-1])
-        rows, S = g2.shape[0], _TallLinear.SLABS
-        dx = (g2 @ weight).view_as(x) if ctx.needs_input_grad[0] else None
-        if rows % S == 0 and rows >= 64 * S:
-            dw = _sum_slabs(torch.bmm(g2.view(S, rows // S, -1).transpose(1, 2), x2.view(S, rows // S, -1)))
-        else:
-            dw = g2.t() @ x2
-        # column sums of a very tall, narrow matrix: torch's reduction takes 0.66 ms for 524 288 x 9; two stages 17 us
-        db = g2.view(1024, rows // 1024, -1).sum(1).sum(0) if rows % 1024 == 0 and rows >= 65536 else g2.sum(0)
-        return dx, dw, db
-
-
-def tall_linear(x, lin):
-    return _TallLinear.apply(x, lin.weight, lin.bias)
-
-
 class MultiHeadedAttention(nn.Module):
     def __init__(self, h, d_model, dropout=0.1, keep_value=False, store_attn=None):
         super().__init__()
@@ -568,17 +527,13 @@ class TransformerDecoderModel(nn.Module):
         """relation_pred (B,K,K,9) from the last encoder layer's attention map and values (:392-397)."""
         rp = self.relation_proposal  # Linear-ReLU-Linear-ReLU-Linear (:319-326)
         sa = self.model.encoder.layers[-1].self_attn
-        # the whole head as one kernel each way (csrc/relation_fused.hip); other widths compose the layers below
-        head = getattr(ops(), "relation_head", None)
-        pred = head(sa.attn, sa.value, rp[0], rp[2], rp[4]) if head is not None else None
-        if pred is None:
-            # feature (P (x) V) + first Linear + ReLU in one kernel: the (B,K,K,128) feature is never formed
+        pred = getattr(ops(), "relation_pred", None)
+        if pred is not None:      # the form that takes the shape (spacap3d_amd/relation.py: tier)
+            ep["relation_pred"] = pred(sa.attn, sa.value, rp[0], rp[2], rp[4])
+        else:                     # a backend with the first layer only (the CPU oracle)
+            from .relation import tall_linear
             hid = ops().relation_layer1(sa.attn, sa.value, rp[0].weight, rp[0].bias)
-            tail = getattr(ops(), "relation_tail", None)
-            pred = tail(hid, rp[2], rp[4]) if (tail is not None and torch.is_grad_enabled()) else None
-            if pred is None:
-                pred = tall_linear(F.relu(tall_linear(hid, rp[2])), rp[4])
-        ep["relation_pred"] = pred
+            ep["relation_pred"] = tall_linear(F.relu(tall_linear(hid, rp[2])), rp[4])
 
     # Decoding attributes (not parameters, not in the state-dict): the beam width and the exponent of the length in the final
     # ranking, read by forward_eval when its arguments are None (engine.Evaluator sets them).  beam_return_all adds every final
@@ -671,9 +626,8 @@ class TransformerDecoderModel(nn.Module):
         caches = [dict() for _ in dec.layers]
         if memory.shape[0] != B * K:  # encoder ran once per scene: the indicator adds that proposal's memory row
             indicator = obj_flat.unsqueeze(1) + memory.reshape(B * K, -1).unsqueeze(1)
-            dec_memory = None
         else:
-            indicator, dec_memory = obj_flat.unsqueeze(1), memory
+            indicator = obj_flat.unsqueeze(1)
         embed, pos = self.model.tgt_embed[0], self.model.tgt_embed[1]
         cd = getattr(ops(), "caption_decode", None)
         fused = self.early_guide and not self.training and cd is not None \
@@ -686,7 +640,7 @@ class TransformerDecoderModel(nn.Module):
                 got = cd.sample_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), sos, eos, MAX_DES_LEN + 1,
                                        S, tau, topk, sample_seed)
                 return self._sample_outputs(ep, B, K, *got)
-            return self._sample_generic(ep, B, K, S, tau, topk, sample_seed, dec, indicator, embed, pos)
+            return self._sample_generic(ep, B, K, S, tau, topk, sample_seed, dec, indicator)
         if beam and fused and not self.beam_generic:
             # the greedy loop below at B K W rows: top-W log-probabilities, one selection per sequence, attention through an
             # ancestor table (caption_decode.beam_decode, csrc/caption_decode.hip)
@@ -696,31 +650,37 @@ class TransformerDecoderModel(nn.Module):
                                  trace=self.last_beam_trace)
             return self._beam_outputs(ep, B, K, *got)
         if beam:
-            return self._beam_generic(ep, B, K, W, alpha, dec, indicator, embed, pos)
+            return self._beam_generic(ep, B, K, W, alpha, dec, indicator)
         if fused:
             # pre-allocated key / value caches, one token per sequence and step, four launches per layer (caption_decode.greedy_decode)
             words = cd.greedy_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), self.word_to_idx["sos"],
                                      MAX_DES_LEN + 1)
             ep["lang_cap"] = words.view(B, K, -1)
             return ep
-        if self.early_guide:
-            # positions: 0 = object indicator, 1.. = words (sinusoid added to the words only, as tgt_embed does)
-            x_new = torch.cat((indicator, pos.dropout(embed(ys) + pos.pe[:, :1])), dim=1)
-            mask = subsequent_mask(2, device=ys.device).expand(B * K, -1, -1)
-            cross_mem, cross_mask = dec_memory, src_mask
-        else:
-            x_new = pos.dropout(embed(ys) + pos.pe[:, :1])
-            mask = None
-            cross_mem, cross_mask = indicator, None  # late guide: cross-attention over the 1-token indicator (:266)
+        words = ys[:, 0]
         for step in range(MAX_DES_LEN + 1):
-            out = decode_incremental(dec, x_new, caches, memory=cross_mem, src_mask=cross_mask, mask=mask)
-            next_word = self.model.generator(out[:, -1, :]).argmax(dim=-1)
-            ys = torch.cat([ys, next_word.unsqueeze(1)], dim=1)
-            t = ys.size(1) - 1  # index of the newest word within the word sequence
-            x_new = pos.dropout(embed(next_word.unsqueeze(1)) + pos.pe[:, t:t + 1])
-            mask = None
+            words = self.model.generator(self._cached_step(dec, caches, indicator, step, words)).argmax(dim=-1)
+            ys = torch.cat([ys, words.unsqueeze(1)], dim=1)
         ep["lang_cap"] = ys[:, 1:].view(B, K, -1)
         return ep
+
+    def _cached_step(self, dec, caches, ind, i, words, parents=None):
+        """The decoder's output row (rows, d_model) for the words (rows,) of step ``i`` through the cached per-operator decoder
+        (``decode_incremental``); ``parents`` (rows,) first reorders the key / value caches of the earlier steps (beam search).
+        Early guide: positions 0 = object indicator ``ind`` (rows, 1, d), 1.. = words (sinusoid added to the words only, as
+        tgt_embed does), so step 0 feeds two positions under a causal mask; late guide: cross-attention over the 1-token
+        indicator (:266)."""
+        embed, pos = self.model.tgt_embed[0], self.model.tgt_embed[1]
+        if parents is not None and i > 0:
+            for c in caches:
+                c["k"], c["v"] = c["k"].index_select(0, parents), c["v"].index_select(0, parents)
+        x_new = pos.dropout(embed(words.unsqueeze(1)) + pos.pe[:, i:i + 1])
+        mask = None
+        if i == 0 and self.early_guide:
+            x_new = torch.cat((ind, x_new), dim=1)
+            mask = subsequent_mask(2, device=words.device).expand(ind.shape[0], -1, -1)
+        out = decode_incremental(dec, x_new, caches, memory=None if self.early_guide else ind, src_mask=None, mask=mask)
+        return out[:, -1, :]
 
     def _beam_outputs(self, ep, B, K, ys, score, beams=None, scores=None, lengths=None):
         ep["lang_cap"] = ys.view(B, K, -1)
@@ -739,14 +699,13 @@ class TransformerDecoderModel(nn.Module):
         ep["lang_cap_sample_lengths"] = length.view(B, K, -1)
         return ep
 
-    def _sample_generic(self, ep, B, K, S, tau, topk, seed, dec, indicator, embed, pos):
+    def _sample_generic(self, ep, B, K, S, tau, topk, seed, dec, indicator):
         """Sampled decoding through the cached per-operator decoder (``decode_incremental``): everything the fused path does not
         take -- late guide, other head counts, the CPU oracle backend.  Row r S + s is sample s of sequence r."""
         from .sampling import sample
         R = B * K
         ind = indicator.repeat_interleave(S, 0)
         caches = [dict() for _ in dec.layers]
-        cross_mem = None if self.early_guide else ind
         seed_dev = None
         if seed is None:   # as the fused path: a host word per call and the device's step counter
             from .attention import _next_seed, rng_state
@@ -754,20 +713,14 @@ class TransformerDecoderModel(nn.Module):
             seed_dev = rng_state(ind.device) if ind.is_cuda else None
 
         def step_fn(i, words):
-            x_new = pos.dropout(embed(words.unsqueeze(1)) + pos.pe[:, i:i + 1])
-            mask = None
-            if i == 0 and self.early_guide:   # positions: 0 = object indicator, 1 = sos
-                x_new = torch.cat((ind, x_new), dim=1)
-                mask = subsequent_mask(2, device=words.device).expand(R * S, -1, -1)
-            out = decode_incremental(dec, x_new, caches, memory=cross_mem, src_mask=None, mask=mask)
-            return self.model.generator.proj(out[:, -1, :])
+            return self.model.generator.proj(self._cached_step(dec, caches, ind, i, words))
 
         got = sample(step_fn, R, S, MAX_DES_LEN + 1, self.word_to_idx["sos"], self.word_to_idx["eos"], tau, topk, seed, seed_dev,
                      device=indicator.device)
         self.last_sample_trace = {"gap": got["gap"]}     # (n_words, R S): for parity tests
         return self._sample_outputs(ep, B, K, got["ys"], got["score"], got["length"])
 
-    def _beam_generic(self, ep, B, K, W, alpha, dec, indicator, embed, pos):
+    def _beam_generic(self, ep, B, K, W, alpha, dec, indicator):
         """Beam search through the cached per-operator decoder (``decode_incremental``): everything the fused path does not
         take -- late guide, other head counts, the CPU oracle backend.  Row r W + w is hypothesis w of sequence r; a selection
         reorders the key / value caches with ``index_select``."""
@@ -775,23 +728,9 @@ class TransformerDecoderModel(nn.Module):
         R = B * K
         ind = indicator.repeat_interleave(W, 0)
         caches = [dict() for _ in dec.layers]
-        # (early guide: the decoder has no cross-attention and never reads the memory; late guide: it attends over the indicator)
-        cross_mem = None if self.early_guide else ind
 
         def step_fn(s, words, parents):
-            if s == 0:
-                x_new = pos.dropout(embed(words.unsqueeze(1)) + pos.pe[:, :1])
-                mask = None
-                if self.early_guide:   # positions: 0 = object indicator, 1 = sos
-                    x_new = torch.cat((ind, x_new), dim=1)
-                    mask = subsequent_mask(2, device=words.device).expand(R * W, -1, -1)
-            else:
-                for c in caches:
-                    c["k"], c["v"] = c["k"].index_select(0, parents), c["v"].index_select(0, parents)
-                x_new = pos.dropout(embed(words.unsqueeze(1)) + pos.pe[:, s:s + 1])
-                mask = None
-            out = decode_incremental(dec, x_new, caches, memory=cross_mem, src_mask=None, mask=mask)
-            return self.model.generator(out[:, -1, :])
+            return self.model.generator(self._cached_step(dec, caches, ind, s, words, parents))
 
         got = beam_search(step_fn, R, W, MAX_DES_LEN + 1, self.word_to_idx["sos"], self.word_to_idx["eos"], alpha,
                           device=indicator.device)

@@ -172,6 +172,7 @@ def test_fused_layernorm_matches_reference_formula(att, shape):
 @pytest.mark.parametrize("B,H,K,D", [(2, 8, 256, 16), (1, 8, 64, 16), (2, 32, 40, 16), (1, 4, 33, 32)])
 def test_relation_feature_matches_reference_chain(att, B, H, K, D):
     """models/transformer_captioner.py:393-396 (repeat / product / transposes / view) and its autograd backward."""
+    from spacap3d_amd import relation as att
     g = torch.Generator().manual_seed(K)
     P = torch.rand(B, H, K, K, generator=g)
     V = torch.randn(B, K, H, D, generator=g).transpose(1, 2)  # the strided view the model passes
@@ -190,6 +191,7 @@ def test_relation_feature_matches_reference_chain(att, B, H, K, D):
 @pytest.mark.parametrize("B,H,K,D", [(2, 8, 256, 16), (1, 8, 50, 16), (1, 4, 33, 32), (2, 32, 24, 4)])
 def test_fused_relation_layer1_matches_feature_linear_relu(att, B, H, K, D):
     """relu(Linear(P (x) V)) of models/transformer_captioner.py:393-397,319-321 without forming the feature."""
+    from spacap3d_amd import relation as att
     g = torch.Generator().manual_seed(K + H)
     C = H * D
     P = torch.rand(B, H, K, K, generator=g)
@@ -371,9 +373,9 @@ def test_conv1x1_channel_major_kernel(B, CO, CI, N):
 
 @pytest.mark.parametrize("shape", [(2, 64, 64, 128), (1, 50, 50, 128), (8192, 128), (77, 128), (1, 128)])
 def test_relation_tail_matches_the_three_module_composition(shape):
-    """linear.RelationTail (Linear(128,128) -> ReLU -> Linear(128,9) of the relation head, one forward kernel + one
+    """relation.RelationTail (Linear(128,128) -> ReLU -> Linear(128,9) of the relation head, one forward kernel + one
     streaming backward kernel + two GEMMs) against float64 autograd of the nn.Module composition."""
-    from spacap3d_amd.linear import relation_tail
+    from spacap3d_amd.relation import relation_tail
     torch.manual_seed(sum(shape))   # (the Linear initialisers draw from the global generator)
     g = torch.Generator().manual_seed(sum(shape))
     lin2, lin3 = torch.nn.Linear(128, 128), torch.nn.Linear(128, 9)
@@ -400,11 +402,12 @@ def test_relation_tail_matches_the_three_module_composition(shape):
 
 @pytest.mark.parametrize("B,K", [(2, 64), (1, 8), (3, 40), (8, 256)])
 def test_relation_head_one_kernel_each_way(B, K):
-    """linear.RelationHead (csrc/relation_fused.hip: feature + Linear-ReLU-Linear-ReLU-Linear of the relation head without
+    """relation.RelationHead (csrc/relation_fused.hip: feature + Linear-ReLU-Linear-ReLU-Linear of the relation head without
     any pair-sized intermediate but hid2) against float64 autograd of the reference composition
-    (models/transformer_captioner.py:319-326, 392-397), values and every gradient; and against the composed
-    relation_layer1 + relation_tail path it replaces."""
-    from spacap3d_amd.linear import relation_head
+    (models/transformer_captioner.py:319-326, 392-397), values and every gradient; and the
+    same head at K - 1 proposals (no one-kernel form: relation_head hands it to relation.RelationWide) and with 5 outputs
+    (neither form: None)."""
+    from spacap3d_amd.relation import relation_head
     H, D = 8, 16
     torch.manual_seed(B * 1000 + K)
     g = torch.Generator().manual_seed(B * 1000 + K)
@@ -439,7 +442,7 @@ def test_relation_head_one_kernel_each_way(B, K):
                 assert float((d > 5e-5).double().mean()) < 5e-3 and float(d.max()) < 0.1, (n, float(d.max()))
             else:
                 assert float(d.max()) < 5e-3, (n, float(d.max()))
-    # K not a multiple of 8: no one-kernel form; the composition of linear.RelationWide (first-layer kernel + tiled split-bf16
+    # K not a multiple of 8: no one-kernel form; the composition of relation.RelationWide (first-layer kernel + tiled split-bf16
     # layer 2 + 9-wide layer 3) takes it, same values
     odd = relation_head(Pg[:, :, :K - 1, :K - 1], Vg[:, :, :K - 1], *lins)
     with torch.no_grad():
@@ -451,7 +454,7 @@ def test_relation_head_one_kernel_each_way(B, K):
 
 @pytest.mark.parametrize("shape", [(8, 256, 128), (8, 32, 128), (3, 7, 300)])
 def test_layernorm_residual_node_adds_both_gradient_paths(att, shape):
-    """attention.FusedLayerNormResidual: (norm(x), x) from one node whose backward kernel adds the residual path's
+    """attention.layer_norm_residual: (norm(x), x) from one node whose backward kernel adds the residual path's
     gradient to the LayerNorm gradient (spacap_layernorm_bwd_add_f32); against float64 autograd of
     x + W norm(x) with the reference's LayerNorm formula (unbiased std, eps on the std)."""
     g = torch.Generator().manual_seed(sum(shape))

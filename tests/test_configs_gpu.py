@@ -254,11 +254,11 @@ def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
 
 def test_cfg5_wide_relation_head_at_full_size_on_sampled_pair_rows():
     """BASELINE config 5 at its full per-GPU size: 16 scenes x 512 x 512 = 4 194 304 proposal pairs, 512 channels, 32 heads
-    (8.6 GB per pair tensor) through linear.RelationWide (models/transformer_captioner.py:319-326, 392-397 at d_model = 512).
+    (8.6 GB per pair tensor) through relation.RelationWide (models/transformer_captioner.py:319-326, 392-397 at d_model = 512).
     Every stage of the head is LOCAL to a pair row -- hid1 row from P[b, :, i, j] and U[b, j], hid2, pred; backward: dz2, dhid1
     and dP[b, :, i, j] -- so 256 sampled rows are recomputed in float64 from the same inputs and compared: forward 3e-6 of scale,
     dP 3e-5 (a hidden unit within fp32 rounding of zero may gate differently: rows with such a unit are excluded, < 2 %)."""
-    from spacap3d_amd.linear import relation_head_wide
+    from spacap3d_amd.relation import relation_head_wide
     B, H, K, D, C = 16, 32, 512, 16, 512
     g = torch.Generator(device=DEV).manual_seed(5)
     torch.manual_seed(5)

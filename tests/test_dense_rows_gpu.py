@@ -67,6 +67,7 @@ def test_vocabulary_projection_reads_and_writes_in_place(lin, B, L, D, V, skip):
 @pytest.mark.parametrize("B,K", [(8, 256), (2, 40), (16, 512)])
 def test_relation_value_projection_per_head(lin, B, K):
     """RelationU against float64 autograd of the einsum it replaces, on the strided view of a packed q | k | v projection."""
+    from spacap3d_amd import relation as lin
     H, D, C = 8, 16, 128
     g = torch.Generator().manual_seed(K)
     qkv = torch.randn(B, K, 3 * H * D, generator=g).to(DEV).requires_grad_(True)

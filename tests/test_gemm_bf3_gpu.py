@@ -60,6 +60,7 @@ def test_tiled_split_bf16_weight_gradient(R, N, K):
 def test_wide_relation_head_matches_float64(lin, C, H, seed):
     """RelationWide (hid1 kernel -> split-bf16 layer 2 -> 9-wide layer 3; backward: tail pass, split-bf16 weight / data gradients,
     first-layer backward) against the float64 composition of models/transformer_captioner.py:392-397 + :319-326."""
+    from spacap3d_amd import relation as lin
     B, K, D = 2, 64, 16
     torch.manual_seed(seed)              # (the Linear layers draw their weights from the global generator)
     g = torch.Generator().manual_seed(C + seed)

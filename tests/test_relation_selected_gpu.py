@@ -92,7 +92,7 @@ def problem(B, K):
 @pytest.mark.parametrize("name", SELECTIONS)
 @pytest.mark.parametrize("B,K", SHAPES)
 def test_sparse_gradients_against_float64(lib, B, K, name):
-    from spacap3d_amd.linear import relation_head
+    from spacap3d_amd.relation import relation_head
     P, V, lins = problem(B, K)
     w, _, _ = weights(name, B, K, seed=B * 100 + K)
     refs = [torch.nn.Linear(l.in_features, l.out_features).double() for l in lins]

@@ -247,6 +247,51 @@ def test_dropout_masks_agree_between_forward_and_backward(tf, kind):
         assert rel(h0, torch.relu(n2.double() @ W1.double().t() + b1.double())) < 2e-6
 
 
+def _node_names(out):
+    seen, todo = set(), [out.grad_fn]
+    while todo:
+        f = todo.pop()
+        if f is not None and f not in seen:
+            seen.add(f)
+            todo += [n for n, _ in f.next_functions]
+    return {type(f).__name__ for f in seen}
+
+
+@pytest.mark.parametrize("p", [0.0, 0.25])
+def test_attention_inside_the_node_equals_the_separate_attention_node(tf, p):
+    """The two forms of the out-projection + first feed-forward node share one body: a stack as built takes AttnFfn1 (attention
+    inside the node), the same stack with ``keep_value`` on takes the attention node + AttnOutFfn1.  Output and input gradient
+    agree at the bars of test_stack_matches_the_per_operator_path; with dropout under a REWOUND host call counter, so both forms
+    draw the same seeds in the same order (attention probability, sub-layer, hidden, per layer) -- a body that handed its forward
+    and its backward different seeds, or the two forms different ones, is off by O(1)."""
+    from spacap3d_amd import attention as att
+    m = _stack("enc", N=2, dff=256, p=p).train()
+    B, L = 2, 32
+    x, g = _rand(B, L, 128, seed=5), _rand(B, L, 128, seed=6)
+    mask = (torch.rand(B, 1, L, generator=torch.Generator().manual_seed(1)) > 0.3).long().to(DEV)
+    mask[..., 0] = 1
+    att._next_seed()
+    saved, word = att._CALL_COUNTER[0], att.rng_state(DEV).clone()
+    att.rng_state(DEV).zero_()
+    res = {}
+    try:
+        for keep, node in ((False, "AttnFfn1Backward"), (True, "AttnOutFfn1Backward")):
+            for l in m.layers:
+                l.self_attn.keep_value = keep
+            att._CALL_COUNTER[0] = 20261003 << 20
+            xi = x.clone().requires_grad_()
+            out = m(xi, mask)
+            names = _node_names(out)
+            assert node in names and not ({"AttnFfn1Backward", "AttnOutFfn1Backward"} - {node}) & names, names
+            (out * g).sum().backward()
+            res[keep] = (out.detach(), xi.grad)
+    finally:
+        att._CALL_COUNTER[0] = saved
+        att.rng_state(DEV).copy_(word)
+    assert rel(res[False][0], res[True][0]) < 1e-5
+    assert rel(res[False][1], res[True][1]) < 5e-5
+
+
 @pytest.mark.parametrize("B,L,mask_kind,p", [(2, 256, "key", 0.0), (3, 32, "causal", 0.0), (2, 256, "key", 0.2), (1, 96, None, 0.0)])
 def test_single_launch_attention_backward_equals_the_two_launch_form(tf, B, L, mask_kind, p):
     """spacap_mha_bwd_delta_f32 (delta = sum_d out d_out handed in, dQ and dK/dV halves in one launch) against

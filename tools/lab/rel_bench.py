@@ -7,7 +7,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-from spacap3d_amd import attention, linear  # noqa: E402
+from spacap3d_amd import relation  # noqa: E402
 from spacap3d_amd._native import check, lib  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -56,11 +56,11 @@ def main():
     Pg = P.clone().requires_grad_(True)
 
     def composed():
-        hid = attention.relation_layer1(Pg, V, lins[0].weight, lins[0].bias)
-        return linear.relation_tail(hid, lins[1], lins[2])
+        hid = relation.relation_layer1(Pg, V, lins[0].weight, lins[0].bias)
+        return relation.relation_tail(hid, lins[1], lins[2])
 
     def fused():
-        return linear.relation_head(Pg, V, *lins)
+        return relation.relation_head(Pg, V, *lins)
 
     for name, fn in (("composed", composed), ("fused", fused)):
         t(fn, f"{name}: forward (autograd on)")
