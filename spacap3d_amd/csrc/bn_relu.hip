@@ -15,6 +15,7 @@
 //             dense pass reads only z.
 // Numerics: PyTorch's formula (biased variance for normalisation, unbiased for running_var, eps inside the
 // sqrt); the statistics are accumulated in fp64, which is at least as accurate as the library's fp32 Welford.
+// A NaN goes through the clamp, wins the max and passes the ReLU's gradient, as in that chain (relu_max.hpp).
 // Everything is deterministic (fixed partial-sum order, no atomics).
 #include <math.h>
 
@@ -22,6 +23,7 @@
 
 #include "common.hpp"
 #include "mfma.hpp"
+#include "relu_max.hpp"
 
 namespace {
 // element index of the float4 group i of channel c: (i / per_b) rows of C * L + (i % per_b) * 4.  i and per_b fit 32 bits on every
@@ -111,16 +113,16 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const float *__restr
     for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < L; i += (long)gridDim.x * 1024) {
       f32x4 v = *reinterpret_cast<const f32x4 *>(zr + i);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = fmaxf((v[u] - mean) * sc + sh, 0.f);
+      for (int u = 0; u < 4; ++u) v[u] = spacap::relu_keep_nan((v[u] - mean) * sc + sh);
       *reinterpret_cast<f32x4 *>(outr + i) = v;
     }
   } else {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < L; i += (long)gridDim.x * 256)
-      outr[i] = fmaxf((zr[i] - mean) * sc + sh, 0.f);
+      outr[i] = spacap::relu_keep_nan((zr[i] - mean) * sc + sh);
   }
 }
 
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+using spacap::better;   // relu_max.hpp: the first maximum, a NaN before any number
 
 // ---- forward apply + max over the S samples of each (b, c, p) row; S in {16, 32, 64, 128}
 template <int S>
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(256) void bn_relu_max_kernel(const float *__restric
     const float mean = stats[c * 2], sc = stats[c * 2 + 1] * gamma[c], sh = beta[c];
     f32x4 v = ok ? *reinterpret_cast<const f32x4 *>(z + row * S + sub * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = fmaxf((v[u] - mean) * sc + sh, 0.f);
+    for (int u = 0; u < 4; ++u) v[u] = spacap::relu_keep_nan((v[u] - mean) * sc + sh);
     float bv = v.x;
     int bi = sub * 4;
 #pragma unroll
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(STAT_THREADS) void bn_bwd_partial_kernel(const floa
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const float xh = (v[u] - mean) * r;
-        const float dy = (xh * g + bt > 0.f) ? d[u] : 0.f;
+        const float dy = spacap::relu_passes(xh * g + bt) ? d[u] : 0.f;
         s1 += dy;
         s2 += (double)dy * xh;
       }
@@ -184,7 +186,7 @@ __global__ __launch_bounds__(STAT_THREADS) void bn_bwd_partial_kernel(const floa
     for (long i = (long)sp * STAT_THREADS + threadIdx.x; i < total; i += (long)nsplit * STAT_THREADS) {
       const size_t off = ((size_t)(i / L) * C + c) * L + i % L;
       const float xh = (z[off] - mean) * r;
-      const float dy = (xh * g + bt > 0.f) ? dA[off] : 0.f;
+      const float dy = spacap::relu_passes(xh * g + bt) ? dA[off] : 0.f;
       s1 += dy;
       s2 += (double)dy * xh;
     }
@@ -210,7 +212,7 @@ __global__ __launch_bounds__(STAT_THREADS) void bn_bwd_pooled_partial_kernel(
   for (long i = (long)sp * STAT_THREADS + threadIdx.x; i < total; i += (long)nsplit * STAT_THREADS) {
     const size_t row = ((size_t)(i / P) * C + c) * P + i % P;
     const float xh = (z[row * S + arg[row]] - mean) * r;
-    const float dy = (xh * g + bt > 0.f) ? dP[row] : 0.f;
+    const float dy = spacap::relu_passes(xh * g + bt) ? dP[row] : 0.f;
     s1 += dy;
     s2 += (double)dy * xh;
   }
@@ -269,7 +271,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dz_kernel(const float *__restrict_
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const float xh = (v[u] - mean) * r;
-        const float dy = (xh * g + bt > 0.f) ? d[u] : 0.f;
+        const float dy = spacap::relu_passes(xh * g + bt) ? d[u] : 0.f;
         o[u] = gr * (dy - k1 - xh * k2);
       }
       *reinterpret_cast<f32x4 *>(dzr + i) = o;
@@ -284,7 +286,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dz_kernel(const float *__restrict_
         d = up[(size_t)row * L + i];
       }
       const float xh = (zr[i] - mean) * r;
-      const float dy = (xh * g + bt > 0.f) ? d : 0.f;
+      const float dy = spacap::relu_passes(xh * g + bt) ? d : 0.f;
       dzr[i] = gr * (dy - k1 - xh * k2);
     }
   }
@@ -322,7 +324,7 @@ __global__ __launch_bounds__(STAT_THREADS) void bn_relu_train_small_kernel(
     const size_t off = group_off(i, per_b, C, c, L);
     f32x4 v = *reinterpret_cast<const f32x4 *>(z + off);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = fmaxf((v[u] - mean) * sc + sh, 0.f);
+    for (int u = 0; u < 4; ++u) v[u] = spacap::relu_keep_nan((v[u] - mean) * sc + sh);
     *reinterpret_cast<f32x4 *>(out + off) = v;
   }
 }
@@ -343,7 +345,7 @@ __global__ __launch_bounds__(STAT_THREADS) void bn_relu_bwd_small_kernel(
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const float xh = (v[u] - mean) * r;
-      const float dy = (xh * g + bt > 0.f) ? d[u] : 0.f;
+      const float dy = spacap::relu_passes(xh * g + bt) ? d[u] : 0.f;
       s1 += dy;
       s2 += (double)dy * xh;
     }
@@ -360,7 +362,7 @@ __global__ __launch_bounds__(STAT_THREADS) void bn_relu_bwd_small_kernel(
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const float xh = (v[u] - mean) * r;
-      const float dy = (xh * g + bt > 0.f) ? d[u] : 0.f;
+      const float dy = spacap::relu_passes(xh * g + bt) ? d[u] : 0.f;
       o[u] = gr * (dy - k1 - xh * k2);
     }
     *reinterpret_cast<f32x4 *>(dz + off) = o;

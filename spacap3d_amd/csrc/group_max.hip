@@ -13,18 +13,13 @@
 
 #include "common.hpp"
 #include "mfma.hpp"
+#include "relu_max.hpp"
 
 namespace {
 
 using spacap::mfma::f32x4;
 
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) {
-  // candidate (v, i) replaces (bv, bi): larger value, NaN beats non-NaN, ties / NaN-NaN keep the lower index
-  const bool vn = v != v, bn = bv != bv;
-  if (vn != bn) return vn;
-  if (vn) return i < bi;
-  return v > bv || (v == bv && i < bi);
-}
+using spacap::better;   // relu_max.hpp
 
 template <int S>
 __global__ __launch_bounds__(256) void group_max_kernel(const float *__restrict__ x, long rows,
