@@ -1082,6 +1082,41 @@ int spacap_caption_score_f64(const int32_t *cand_tok, const int32_t *cand_len, i
                              const uint64_t *df_code, const double *df_idf, const int64_t *df_off, double log_nkeys,
                              int32_t *bleu, double *rouge, double *cider, spacap_stream_t stream);
 
+/* ---- self-critical caption training (the reference has none; csrc/caption_reward.hip, scst_loss.hip) --- */
+
+/* CIDEr-D of every DRAWN caption against the references of its scene's key row; one wave per row, one launch, no atomics, no
+ * state: a captured call replays.  tokens i64 [rows, L] decoded words; row r belongs to scene r / rows_per_scene, whose key row
+ * is key_table[dataset_idx[b], object_id[b]] (i64 [rows / rows_per_scene] each; key_table i32 [n_items, n_obj]; an index outside
+ * its table or an entry outside 0..nkeys-1: no row).  The caption is sos, the words through the first eos, an eos appended when
+ * there was none.  References and document frequencies exactly as spacap_caption_score_f64 takes them (df_off: 5 int64 ON THE
+ * HOST).  Writes cider f64 [rows] -- the number spacap_caption_score_f64 writes for this caption as its key's candidate, 0
+ * without a key row --, key i32 [rows] (-1: no row), length i32 [rows] (the decoded words through the first eos, L: none) and
+ * tf_tok i64 [rows, L + 2]: sos, those words, zeros behind them.
+ * rows >= 0 a multiple of rows_per_scene >= 1, L + 2 <= 64, 0 <= sos, eos <= 65535.  rows = 0 is a no-op. */
+int spacap_caption_reward_f64(const int64_t *tokens, int rows, int rows_per_scene, int L, const int64_t *dataset_idx,
+                              const int64_t *object_id, const int32_t *key_table, int n_items, int n_obj, int nkeys, int sos,
+                              int eos, const int32_t *ref_tok, int64_t n_tok, const int32_t *ref_off, const int32_t *ref_len,
+                              int64_t n_ref, const int32_t *key_ref_off, const uint64_t *df_code, const double *df_idf,
+                              const int64_t *df_off, double log_nkeys, double *cider, int32_t *key, int32_t *length,
+                              int64_t *tf_tok, spacap_stream_t stream);
+
+/* The reward-weighted loss over the drawn words.  logits f32 [R, W, V], words i64 [R, W], length i32 [R] (positions t <
+ * length[r] count; clamped to 0..W), reward f64 [R], baseline f64 [R / S] or NULL (leave-one-out: the mean of the scene's
+ * other S - 1 rewards; needs S >= 2), count u8 [R / S]; row r = b S + s.
+ *   A_r = count[b] ? fp32(reward[r] - base) : 0;   loss = - sum_r A_r sum_{t < length_r} logp[r,t,words[r,t]] / (sum_r count[b] length_r + 1e-6)
+ * A word id outside [0, V) contributes nothing.  Forward writes pair f32 [R, W, 2] = (log-sum-exp, the drawn word's log-
+ * probability; zeros behind length), hit u8 [R, W] (workspace), adv f32 [R], rowlogp f32 [R] = sum_{t < length} logp, and
+ * out f32 [8] = (loss, share of counted positions whose first arg-max is the drawn word, 1 / (sum count length + 1e-6), counting
+ * scenes, mean reward and mean baseline over the counting rows, 0, 0).  No log-probability image; positions behind length read
+ * no logits; sums over rows in a fixed order by one wave (bitwise reproducible).  Two launches.  R = 0: out zeroed.
+ * Backward (one launch): dlogits f32 [R, W, V] = gloss[0] (-A_r out[2]) ([v == words[r,t]] - softmax) for t < length[r], exact
+ * zeros everywhere else (every element is written). */
+int spacap_scst_loss_fwd_f32(const float *logits, const int64_t *words, const int32_t *length, const double *reward,
+                             const double *baseline, const uint8_t *count, int R, int S, int W, int V, float *pair, uint8_t *hit,
+                             float *adv, float *rowlogp, float *out, spacap_stream_t stream);
+int spacap_scst_loss_bwd_f32(const float *logits, const int64_t *words, const int32_t *length, const float *pair, const float *adv,
+                             const float *out, const float *gloss, int R, int W, int V, float *dlogits, spacap_stream_t stream);
+
 /* ---- dense-caption predictions (replaces the host loop a caller of the reference writes over parse_predictions with
  * per_class_proposal=False, lib/ap_helper.py:145-158, and decode_caption, lib/eval_helper.py:46-57; csrc/predictions.hip) --- */
 

@@ -99,6 +99,10 @@ SIGNATURES = {
     "spacap_caption_select_i32": (_i, [_p] * 6 + [_i] * 4 + [_p] + [_i] * 5 + [_p] * 4 + [_p]),
     "spacap_caption_score_f64": (_i, [_p, _p, _i, _p, ctypes.c_int64, _p, _p, ctypes.c_int64, _p, _p, _p, _p,
                                       ctypes.c_double, _p, _p, _p, _p]),
+    "spacap_caption_reward_f64": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, ctypes.c_int64, _p, _p, ctypes.c_int64,
+                                       _p, _p, _p, _p, ctypes.c_double, _p, _p, _p, _p, _p]),
+    "spacap_scst_loss_fwd_f32": (_i, [_p] * 6 + [_i] * 4 + [_p] * 5 + [_p]),
+    "spacap_scst_loss_bwd_f32": (_i, [_p] * 7 + [_i] * 3 + [_p, _p]),
     "spacap_dense_caption_select": (_i, [_p] * 5 + [_i] * 5 + [_p] * 7 + [_p]),
     "spacap_multiview_workspace_bytes": (ctypes.c_size_t, [_i]),
     "spacap_multiview_map_f32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, ctypes.c_size_t, _p, _p]),

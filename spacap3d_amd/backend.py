@@ -40,6 +40,7 @@ class HipBackend:
         self.detection_losses = _fl.detection_losses
         self.relation_losses = _fl.relation_losses
         self.caption_head_loss = _fl.caption_head_loss
+        self.self_critical_loss = _fl.self_critical_loss
         self.loss_tail = _fl.loss_tail
         self.proposal_decode = _fl.proposal_decode
         self.l2norm_rows = _fl.l2norm_rows

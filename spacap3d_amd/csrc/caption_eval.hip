@@ -24,15 +24,14 @@
 // reference's order: bit-equal to Python's.  CIDEr's sums run in wave-reduction order, not the reference's dict order.
 #include <math.h>
 
-#include "eval_common.hpp"
+#include "cider_common.hpp"
 
 namespace {
 
 using namespace spacap::eval;
 
-constexpr int CE_LMAX = 64;                         // tokens per sentence = lanes of a wave = bits of the LCS word
+// (CE_LMAX = 64 tokens per sentence = lanes of a wave = bits of the LCS word: cider_common.hpp)
 constexpr double CE_BETA2 = 1.2 * 1.2;              // rouge.py: self.beta ** 2
-constexpr double CE_TWO_SIGMA2 = 2.0 * 6.0 * 6.0;   // cider_scorer.py: 2 * sigma ** 2
 
 struct SelectArgs {
   const int64_t *tokens;             // [B,K,L]
@@ -86,41 +85,15 @@ __global__ __launch_bounds__(CE_LMAX) void caption_write_kernel(SelectArgs a) {
 struct ScoreArgs {
   const int32_t *cand_tok;      // [NKEYS, 64]
   const int32_t *cand_len;      // [NKEYS]
-  const int32_t *ref_tok;       // CSR over the references
-  const int32_t *ref_off;       // [NREF]
-  const int32_t *ref_len;       // [NREF]
-  const int32_t *key_ref_off;   // [NKEYS + 1]
-  const uint64_t *df_code;      // the four sorted tables, one after the other
-  const double *df_idf;         // log(NKEYS) - log(max(1, df)) per entry
-  long long df_off[5];          // table n (n-grams of n words) = entries df_off[n-1] .. df_off[n]
-  long long n_tok, n_ref;
-  double log_nkeys;
+  CiderRefs refs;               // the references (CSR) and the key rows' ranges
+  CiderTables df;               // the document-frequency tables
   int32_t *bleu;                // [NKEYS, 10]: testlen, reflen, guess[4], correct[4]
   double *rouge;                // [NKEYS]
   double *cider;                // [NKEYS]
 };
 
-// n-gram codes of the sentence in s_tok (len tokens) at this lane's position: code[n-1] is valid when lane + n <= len
-__device__ __forceinline__ void ngram_codes(const int *s_tok, int lane, uint64_t code[4]) {
-  uint64_t c = 0;
-#pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    const int t = lane + n < CE_LMAX ? s_tok[lane + n] : 0;
-    c = (c << 16) | (uint64_t)(t & 0xFFFF);
-    code[n] = c;
-  }
-}
-
-__device__ __forceinline__ double idf_lookup(const ScoreArgs &a, int n, uint64_t code) {
-  long long lo = a.df_off[n], hi = a.df_off[n + 1];
-  while (lo < hi) {
-    const long long mid = (lo + hi) >> 1;
-    if (a.df_code[mid] < code) lo = mid + 1;
-    else hi = mid;
-  }
-  return (lo < a.df_off[n + 1] && a.df_code[lo] == code) ? a.df_idf[lo] : a.log_nkeys;
-}
-
+// (the n-gram codes, the idf lookup and CIDEr's per-candidate and per-reference bodies: cider_common.hpp, shared with
+// caption_reward.hip)
 __global__ __launch_bounds__(CE_LMAX) void caption_score_kernel(ScoreArgs a) {
   __shared__ int s_tok[CE_LMAX];
   __shared__ uint64_t s_cc[4][CE_LMAX];             // candidate n-gram codes
@@ -137,48 +110,21 @@ __global__ __launch_bounds__(CE_LMAX) void caption_score_kernel(ScoreArgs a) {
   for (int n = 0; n < 4; ++n) s_cc[n][lane] = cc[n];
   __syncthreads();
 
-  // candidate: first occurrence, term frequency, tf-idf, norm per n
-  bool cfirst[4];
-  int ccount[4], maxref[4];
-  double cidf[4], cvec[4], cnorm[4], score[4];
+  CiderCand c;
+  cider_candidate(a.df, s_cc, cc, lc, lane, c);
+  int maxref[4];
+  double score[4];
 #pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    const int valid = lc - n;                        // positions 0 .. valid-1 hold an (n+1)-gram
-    const bool in = lane < valid;
-    int cnt = 0, before = 0;
-    for (int j = 0; j < valid; ++j) {
-      const bool eq = s_cc[n][j] == cc[n];
-      cnt += eq ? 1 : 0;
-      before += (eq && j < lane) ? 1 : 0;
-    }
-    cfirst[n] = in && before == 0;
-    ccount[n] = cnt;
-    maxref[n] = 0;
-    cidf[n] = in ? idf_lookup(a, n, cc[n]) : 0.0;
-    cvec[n] = (double)cnt * cidf[n];
-    cnorm[n] = sqrt(spacap::wave_sum(cfirst[n] ? cvec[n] * cvec[n] : 0.0));
-    score[n] = 0.0;
-  }
-  const int len_h = lc > 1 ? lc - 1 : 0;             // the reference's `length`: the number of BIGRAMS
+  for (int n = 0; n < 4; ++n) maxref[n] = 0, score[n] = 0.0;
 
-  long long r0 = a.key_ref_off[key], r1 = a.key_ref_off[key + 1];
+  long long r0 = a.refs.key_ref_off[key], r1 = a.refs.key_ref_off[key + 1];
   r0 = r0 < 0 ? 0 : r0;
-  r1 = r1 > a.n_ref ? a.n_ref : r1;
+  r1 = r1 > a.refs.n_ref ? a.refs.n_ref : r1;
   int best_diff = 0x7fffffff, best_len = 0;
   double pmax = 0.0, rmax = 0.0;
   for (long long r = r0; r < r1; ++r) {              // (uniform over the wave)
-    int lr = a.ref_len[r];
-    lr = lr < 0 ? 0 : (lr > CE_LMAX ? CE_LMAX : lr);
-    const long long off = a.ref_off[r];
-    const bool ok = off >= 0 && off + lr <= a.n_tok;
-    __syncthreads();                                 // the previous reference's readers are done
-    s_tok[lane] = (ok && lane < lr) ? a.ref_tok[off + lane] : -2;
-    __syncthreads();
     uint64_t rc[4];
-    ngram_codes(s_tok, lane, rc);
-#pragma unroll
-    for (int n = 0; n < 4; ++n) s_rc[n][lane] = rc[n];
-    __syncthreads();
+    const int lr = cider_stage_reference(a.refs, r, lane, s_tok, s_rc, rc);
 
     // BLEU "closest" reference length: min over (|l - testlen|, l)
     const int diff = lr > lc ? lr - lc : lc - lr;
@@ -201,33 +147,12 @@ __global__ __launch_bounds__(CE_LMAX) void caption_score_kernel(ScoreArgs a) {
     pmax = prec > pmax ? prec : pmax;
     rmax = rec > rmax ? rec : rmax;
 
-    const int len_r = lr > 1 ? lr - 1 : 0;
-    const double delta = (double)(len_h - len_r);
-    const double penalty = exp(-(delta * delta) / CE_TWO_SIGMA2);
+    const double penalty = cider_penalty(lc, lr);
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
-      const int rvalid = lr - n;
-      // the reference's own vector: norm over its distinct n-grams
-      int rcnt = 0, rbefore = 0, cr = 0;
-      for (int j = 0; j < rvalid; ++j) {
-        const uint64_t x = s_rc[n][j];
-        const bool eq = x == rc[n];
-        rcnt += eq ? 1 : 0;
-        rbefore += (eq && j < lane) ? 1 : 0;
-        cr += x == cc[n] ? 1 : 0;                    // this lane's CANDIDATE n-gram in the reference
-      }
-      const bool rfirst = lane < rvalid && rbefore == 0;
-      double rv = 0.0;
-      if (rfirst) rv = (double)rcnt * idf_lookup(a, n, rc[n]);
-      const double rnorm = sqrt(spacap::wave_sum(rfirst ? rv * rv : 0.0));
-      if (cfirst[n]) maxref[n] = cr > maxref[n] ? cr : maxref[n];
-      double term = 0.0;
-      if (cfirst[n]) {
-        const double vr = (double)cr * cidf[n];
-        term = (cvec[n] < vr ? cvec[n] : vr) * vr;
-      }
-      double val = spacap::wave_sum(term);
-      if (cnorm[n] != 0.0 && rnorm != 0.0) val /= cnorm[n] * rnorm;
+      int cr;
+      double val = cider_reference(a.df, s_rc, rc, cc, c, lr, lane, n, cr);
+      if (c.first[n]) maxref[n] = cr > maxref[n] ? cr : maxref[n];
       val *= penalty;
       score[n] += val;
     }
@@ -236,7 +161,7 @@ __global__ __launch_bounds__(CE_LMAX) void caption_score_kernel(ScoreArgs a) {
   int correct[4];
 #pragma unroll
   for (int n = 0; n < 4; ++n)
-    correct[n] = spacap::wave_sum(cfirst[n] ? (ccount[n] < maxref[n] ? ccount[n] : maxref[n]) : 0);
+    correct[n] = spacap::wave_sum(c.first[n] ? (c.count[n] < maxref[n] ? c.count[n] : maxref[n]) : 0);
   if (lane == 0) {
     int32_t *o = a.bleu + (size_t)key * 10;
     o[0] = lc;
@@ -249,10 +174,7 @@ __global__ __launch_bounds__(CE_LMAX) void caption_score_kernel(ScoreArgs a) {
     double rouge = 0.0;
     if (pmax != 0.0 && rmax != 0.0) rouge = ((1.0 + CE_BETA2) * pmax * rmax) / (rmax + CE_BETA2 * pmax);
     a.rouge[key] = rouge;
-    double avg = (((score[0] + score[1]) + score[2]) + score[3]) / 4.0;
-    const long long nref = r1 - r0;
-    if (nref > 0) avg /= (double)nref;
-    a.cider[key] = avg * 10.0;
+    a.cider[key] = cider_finish(score, r1 - r0);
   }
 }
 
@@ -320,16 +242,16 @@ extern "C" int spacap_caption_score_f64(const int32_t *cand_tok, const int32_t *
   ScoreArgs a;
   a.cand_tok = cand_tok;
   a.cand_len = cand_len;
-  a.ref_tok = ref_tok;
-  a.ref_off = ref_off;
-  a.ref_len = ref_len;
-  a.key_ref_off = key_ref_off;
-  a.df_code = df_code;
-  a.df_idf = df_idf;
-  for (int i = 0; i < 5; ++i) a.df_off[i] = df_off[i];
-  a.n_tok = n_tok;
-  a.n_ref = n_ref;
-  a.log_nkeys = log_nkeys;
+  a.refs.ref_tok = ref_tok;
+  a.refs.ref_off = ref_off;
+  a.refs.ref_len = ref_len;
+  a.refs.key_ref_off = key_ref_off;
+  a.refs.n_tok = n_tok;
+  a.refs.n_ref = n_ref;
+  a.df.df_code = df_code;
+  a.df.df_idf = df_idf;
+  for (int i = 0; i < 5; ++i) a.df.df_off[i] = df_off[i];
+  a.df.log_nkeys = log_nkeys;
   a.bleu = bleu;
   a.rouge = rouge;
   a.cider = cider;

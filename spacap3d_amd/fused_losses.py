@@ -175,6 +175,69 @@ def caption_head_loss(logits, lang_ids, good):
     return logp, out[0], out[1], out
 
 
+class SelfCriticalLoss(Function):
+    """logits (R, W, V) of the teacher-forced pass over R = B S drawn captions -> (out (8,) = (loss, accuracy, 1 / (counted
+    positions + 1e-6), counting scenes, mean reward, mean baseline, 0, 0), advantage (R,), per-row sum of log-probabilities (R,)):
+    the reward-weighted loss of self-critical training as two launches forward and one backward
+    (csrc/scst_loss.hip).  ``words`` (R, W) int64 are the drawn words, ``length`` (R,) int32 how many of them count,
+    ``reward`` (R,) float64, ``baseline`` (B,) float64 or None (leave-one-out over the scene's other samples), ``count`` (B,)
+    which scenes count.  No log-probability image is written: the backward reads the logits again.  Only ``out[0]`` is
+    differentiable."""
+
+    @staticmethod
+    def forward(ctx, logits, words, length, reward, baseline, count, S):
+        if not logits.is_cuda:
+            raise RuntimeError("self_critical_loss: CPU not supported")
+        logits = logits.contiguous()
+        R, W, V = logits.shape
+        S = int(S)
+        dev = logits.device
+        words = words.contiguous()
+        length = length.to(torch.int32).contiguous()
+        reward = reward.to(torch.float64).contiguous()
+        base = baseline.to(torch.float64).contiguous() if baseline is not None else None
+        c8 = count.to(torch.uint8).contiguous()
+        if words.dtype != torch.int64 or tuple(words.shape) != (R, W) or length.numel() != R or reward.numel() != R or S < 1 \
+                or R % S or c8.numel() * S != R or (base is not None and base.numel() * S != R):
+            raise RuntimeError(f"self_critical_loss: expected words ({R}, {W}) int64, length / reward ({R},), baseline / count "
+                               f"({R}/S,) with S={S}; got {tuple(words.shape)} {words.dtype}, {tuple(length.shape)}, "
+                               f"{tuple(reward.shape)}, {None if base is None else tuple(base.shape)}, {tuple(c8.shape)}")
+        with torch.cuda.device(dev):
+            pair = torch.empty(R, W, 2, dtype=torch.float32, device=dev)
+            hit = torch.empty(R, W, dtype=torch.uint8, device=dev)
+            adv = torch.empty(R, dtype=torch.float32, device=dev)
+            rowlogp = torch.empty(R, dtype=torch.float32, device=dev)
+            out = torch.empty(8, dtype=torch.float32, device=dev)
+            check(lib.spacap_scst_loss_fwd_f32(logits.data_ptr(), words.data_ptr(), length.data_ptr(), reward.data_ptr(),
+                                               base.data_ptr() if base is not None else None, c8.data_ptr(), R, S, W, V,
+                                               pair.data_ptr(), hit.data_ptr(), adv.data_ptr(), rowlogp.data_ptr(), out.data_ptr(),
+                                               torch.cuda.current_stream(dev).cuda_stream), "spacap_scst_loss_fwd_f32")
+        ctx.save_for_backward(logits, words, length, pair, adv, out)
+        ctx.mark_non_differentiable(adv, rowlogp)
+        ctx.set_materialize_grads(False)
+        return out, adv, rowlogp
+
+    @staticmethod
+    def backward(ctx, g_out, g_adv, g_rowlogp):
+        if g_adv is not None or g_rowlogp is not None:
+            raise RuntimeError("self_critical_loss: only the loss (out[0]) is differentiable")
+        logits, words, length, pair, adv, out = ctx.saved_tensors
+        R, W, V = logits.shape
+        dev = logits.device
+        gl = g_out[0:1].contiguous()
+        with torch.cuda.device(dev):
+            dlogits = torch.empty_like(logits)
+            check(lib.spacap_scst_loss_bwd_f32(logits.data_ptr(), words.data_ptr(), length.data_ptr(), pair.data_ptr(), adv.data_ptr(),
+                                               out.data_ptr(), gl.data_ptr(), R, W, V, dlogits.data_ptr(),
+                                               torch.cuda.current_stream(dev).cuda_stream), "spacap_scst_loss_bwd_f32")
+        return dlogits, None, None, None, None, None, None
+
+
+def self_critical_loss(logits, words, length, reward, baseline, count, S):
+    """(out (8,), advantage (R,), row log-probabilities (R,)) -- see SelfCriticalLoss."""
+    return SelfCriticalLoss.apply(logits, words, length, reward, baseline, count, S)
+
+
 class ProposalDecode(Function):
     """(net (B,CH,K), agg_xyz (B,K,3), mean_size (NS,3)) -> (nt (B,K,CH), center, heading_residuals, size_residuals, bbox_corner
     f64 (B,K,8,3), bbox_mask, sem_cls, size_cls): decode_scores + decode_pred_box (models/proposal_module.py:81-158) as one

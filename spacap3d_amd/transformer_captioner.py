@@ -443,12 +443,18 @@ class TransformerDecoderModel(nn.Module):
         prep = getattr(ops(), "caption_prep", None) if (src.is_cuda and self.early_guide and self.model.encoder is not None) else None
         src_mask = ep["bbox_mask"].unsqueeze(1)
         x0 = out_full = None
+        scst = self.self_critical if self.training else None
+        if scst is not None and prep is None:
+            raise RuntimeError("self_critical: CPU tensors, a backend without caption_prep, the late guide and a captioner without "
+                               "the Transformer encoder are not supported")
         if prep is not None:
             # encoder first, then nearest proposal + object indicator + token embedding + positional encoding + dropout + mask
             # as one launch (csrc/caption_prep.hip) and the decoder stack on its output
             memory = self.model.encode(src, src_pos, src_mask)
             if self.check_relation:
                 self._relation_head_forked(ep)
+            if scst is not None:
+                return self._self_critical_train(ep, scst, prep, src, memory)
             te = self.model.tgt_embed
             got = prep(ep["aggregated_vote_xyz"], ep["ref_center_label"], src, memory, ep["lang_label"], te[0], te[1])
             if got is not None:
@@ -492,6 +498,68 @@ class TransformerDecoderModel(nn.Module):
         ep["good_bbox_masks"] = good
         if self.check_relation and "relation_pred" not in ep:
             self._relation_head(ep)
+        return ep
+
+    # Self-critical training: None = off, else a self_critical.SelfCritical.  A plain attribute, not in the
+    # state dict; read in training mode only.
+    self_critical = None
+
+    def _self_critical_train(self, ep, sc, prep, src, memory):
+        """The captioner's part of a self-critical training step, after the encoder and the relation head: S captions drawn for
+        the referred object's proposal (and, with the greedy baseline, its greedy caption), their CIDEr-D rewards, the
+        teacher-forced pass over the samples and the reward-weighted loss in place of the cross-entropy.  Drawing and scoring run
+        under ``no_grad`` through the cached decode kernels (no dropout); only the teacher-forced pass is differentiated.  No
+        value is read back on the host."""
+        for k in ("object_id", "dataset_idx"):
+            if k not in ep:
+                raise KeyError(f"self_critical: the batch has no {k!r}")
+        cd = getattr(ops(), "caption_decode", None)
+        loss_op = getattr(ops(), "self_critical_loss", None)
+        te, dec, gen = self.model.tgt_embed, self.model.decoder, self.model.generator
+        B, _, D = src.shape
+        S, n_words = sc.num_samples, MAX_DES_LEN + 1
+        with torch.no_grad():
+            # the nearest proposal and whether it is good, as the cross-entropy path finds them: a B-row caption_prep over two
+            # token columns (no word row is embedded), outside autograd -- the embedding table keeps ONE use in the graph
+            got = prep(ep["aggregated_vote_xyz"], ep["ref_center_label"], src, memory,
+                       torch.ones(B, 2, dtype=torch.int64, device=src.device), te[0], te[1])
+            if got is None or cd is None or loss_op is None:
+                raise RuntimeError("self_critical: these tensors are not supported by the fused caption path")
+            _, _, idx, _, good, pred_ious = got
+            sel = idx.view(B, 1, 1).expand(B, 1, D)
+            indicator = (src.gather(1, sel) + memory.gather(1, sel)).squeeze(1)
+            if not cd.decode_supported(dec.layers, indicator, n_words):
+                raise RuntimeError("self_critical: this decoder stack is not supported by the fused decode")
+            ys, score, _ = cd.sample_decode(dec, gen, te[0], te[1].pe, indicator, sc.sos, sc.eos, n_words, S, sc.temperature,
+                                            sc.top_k, sc.seed)
+            didx, oid = ep["dataset_idx"].reshape(-1), ep["object_id"].reshape(-1)
+            words = ys.view(B * S, n_words)
+            reward, key, length, tf_tok = sc.rewards(words, didx, oid, S)
+            base = None
+            if sc.baseline == "greedy":
+                base = sc.rewards(cd.greedy_decode(dec, gen, te[0], te[1].pe, indicator, sc.sos, n_words), didx, oid, 1)[0]
+            count = good & (key.view(B, S)[:, 0] >= 0)
+            # the token row caption_prep reads is lang_label's layout: one leading column, then sos and the words (tf_tok is
+            # lang_ids' layout); its T = n_words + 2 columns give one logit row per decoded word
+            tok = torch.cat([torch.ones(B * S, 1, dtype=torch.int64, device=src.device), tf_tok[:, :-1]], 1)
+        rep = lambda t: t.repeat_interleave(S, 0)      # autograd sums the S gradients of every scene row
+        got = prep(rep(ep["aggregated_vote_xyz"]), rep(ep["ref_center_label"]), rep(src), rep(memory), tok, te[0], te[1])
+        if got is None:
+            raise RuntimeError("self_critical: these tensors are not supported by the fused caption path")
+        x0, m8 = got[0], got[1]
+        out_full = dec(x0, None, None, m8)
+        vp = getattr(ops(), "vocab_projection", None)
+        logits = vp(out_full, gen.proj, 1) if vp is not None else None
+        if logits is None:
+            logits = gen.proj(out_full[:, 1:, :])
+        out, adv, rowlogp = loss_op(logits, words, length, reward, base, count, S)
+        ep["_cap_loss"] = (out[0], out[1])
+        ep["match_idx"], ep["pred_ious"], ep["good_bbox_masks"] = idx, pred_ious, good
+        ep["scst_samples"], ep["scst_reward"] = ys, reward.view(B, S)
+        ep["scst_baseline"] = base if base is not None else reward.view(B, S).mean(1)
+        ep["scst_advantage"], ep["scst_logp"] = adv.view(B, S), rowlogp.view(B, S)
+        ep["scst_sample_scores"], ep["scst_count"] = score, count
+        ep["scst_stats"] = out.detach()
         return ep
 
     # The relation head reads the last encoder layer only and the decoder reads the encoder's output only: the two are independent
