@@ -114,8 +114,9 @@ def _sa1_vs_float64(C, seed):
     new_xyz, out, inds = sa(xyz, feats)
     assert point_major_of(out) is not None, "the fused shared-MLP path did not run"
     node = _fused_node(out)
-    saved = node.saved_tensors
-    zs, sts, arg = saved[7:10], saved[10:13], saved[14]
+    from spacap3d_amd.sa_mlp import Saved
+    saved = Saved(*node.saved_tensors)
+    zs, sts, arg = (saved.z1, saved.z2, saved.z3), (saved.st1, saved.st2, saved.st3), saved.arg
     wsum = torch.randn(out.shape, device=DEV)
     (out * wsum).sum().backward()
     got = [l.conv.weight.grad.view(l.conv.out_channels, -1).double() for l in sa.mlp_module.children()]
@@ -124,8 +125,8 @@ def _sa1_vs_float64(C, seed):
         B, P, Sn = idx.shape
         flat = idx.view(B, -1)
         # the kernels' selections: relu'(bn(z_k)) with the fp32 expression of the kernels, arg-max of the pooled layer
-        # (the pooled last layer stores no pre-activation any more, only its value at the arg-max rows, saved[9] of shape
-        # (B, P, C3): the frozen restatement gathers the arg-max rows, so that mask is all it needs of the last layer)
+        # (the pooled last layer stores its pre-activation z3 (B * P * S, C3) like the others, and its value at the arg-max
+        # rows beside it (saved.zmax); the frozen restatement gathers the arg-max rows of the mask made from z3)
         masks = [(((z - st[:, 0]) * st[:, 2] + st[:, 3]) > 0).view(B, P, -1, z.shape[-1]).expand(B, P, Sn, -1)
                  for z, st in zip(zs, sts)]
         argl = arg.view(B, P, 1, -1).long()
