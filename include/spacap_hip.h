@@ -340,6 +340,22 @@ int spacap_caption_prep_fwd_f32(const float *xyz, const float *ref, const float 
 int spacap_caption_prep_bwd_f32(const float *g, const int64_t *tok, const int64_t *idx, int B, int K, int D, int T, int V,
                                 float p, uint64_t seed, const uint64_t *seed_dev, float *d_rows, float *d_emb,
                                 spacap_stream_t stream);
+/* The same decoder input with the proposal given by index (the reference has none).  R = B M S rows in
+ * NG = B M groups of S: row r belongs to group r / S, the group to scene (r / S) / M.  src / memory f32 [B,K,D] (memory may be
+ * NULL), prop i64 [NG], tok i64 [R,T], emb, pe as above.
+ *   x0 f32 [R,L,D]: row 0 = src[b,k] + memory[b,k] with k = prop[group], exact zeros for an empty group (k outside 0..K-1);
+ *   row 1+t and mask u8 [R,L,L] exactly what spacap_caption_prep_fwd_f32 writes for a batch of R rows (the same dropout hash
+ *   over the same element index).  No idx / dist / good / pred / counter.  One launch, no state.  R <= 65535. */
+int spacap_caption_prep_rows_fwd_f32(const float *src, const float *memory, const int64_t *prop, const int64_t *tok,
+                                     const float *emb, const float *pe, int B, int K, int M, int S, int D, int T, int V, float p,
+                                     uint64_t seed, const uint64_t *seed_dev, float *x0, uint8_t *mask, spacap_stream_t stream);
+/* g f32 [R,L,D] -> d_rows f32 [B,K,D] (may be NULL): d_rows[b,k] = the fp32 sum of g[r,0] over the groups of scene b with
+ * prop == k, in ascending group and then ascending sample order, starting from 0; exact zero where no group points; empty
+ * groups are skipped; every element is written.  d_emb f32 [V,D] as spacap_caption_prep_bwd_f32 computes it for R rows.  One
+ * launch, no atomics: bitwise reproducible.  D <= 1024, R <= 65535. */
+int spacap_caption_prep_rows_bwd_f32(const float *g, const int64_t *tok, const int64_t *prop, int B, int K, int M, int S, int D,
+                                     int T, int V, float p, uint64_t seed, const uint64_t *seed_dev, float *d_rows, float *d_emb,
+                                     spacap_stream_t stream);
 
 /* ---- LayerNorm of the Transformer (replaces models/transformer_captioner.py:102-113) ----------- */
 
@@ -1116,6 +1132,22 @@ int spacap_scst_loss_fwd_f32(const float *logits, const int64_t *words, const in
                              float *adv, float *rowlogp, float *out, spacap_stream_t stream);
 int spacap_scst_loss_bwd_f32(const float *logits, const int64_t *words, const int32_t *length, const float *pair, const float *adv,
                              const float *out, const float *gloss, int R, int W, int V, float *dlogits, spacap_stream_t stream);
+
+/* The (proposal, object) pairs of a scene that self-critical training rewards (csrc/scst_select.hip).
+ * xyz f32 [B,K,3] proposal centres, center_label f32 [B,G,3], box_label_mask f32 [B,G], scene_object_ids i64 [B,G],
+ * dataset_idx i64 [B], key_table i32 [n_items, n_obj].  Object slot j of scene b is a candidate when box_label_mask[b,j] > 0
+ * and key_table[dataset_idx[b]][scene_object_ids[b,j]] is in 0..nkeys-1 (an index outside its table gives no row).  Its
+ * proposal is argmin_k d(b,k,j), first minimum, d = ((x - cx)^2 + (z - cz)^2) + (y - cy)^2 in un-contracted fp32 (the
+ * expression of spacap_caption_prep_fwd_f32); a NaN distance is never a minimum and an object without a finite minimum does
+ * not qualify.  It qualifies when d < near2, strictly.  The qualifying objects ranked by (d, j) ascending fill the slots
+ * 0 .. n_sel-1 of prop i64 [B,M] (the proposal), obj i64 [B,M] (the object id), slot_of i32 [B,M] (j), key i32 [B,M] (the key
+ * row) and dist f32 [B,M]; the slots behind them hold -1, -1, -1, -1, +inf; n_sel i32 [B] <= M.  Every element is written.  Two
+ * objects may share a proposal.  One launch, one workgroup per scene, no atomics, no state: a captured call replays.
+ * B >= 0 (0: a no-op), K >= 1, 1 <= G <= 256, 1 <= M <= G. */
+int spacap_scst_select_f32(const float *xyz, const float *center_label, const float *box_label_mask,
+                           const int64_t *scene_object_ids, const int64_t *dataset_idx, const int32_t *key_table, int B, int K,
+                           int G, int M, int n_items, int n_obj, int nkeys, float near2, int64_t *prop, int64_t *obj,
+                           int32_t *slot_of, int32_t *key, float *dist, int32_t *n_sel, spacap_stream_t stream);
 
 /* ---- dense-caption predictions (replaces the host loop a caller of the reference writes over parse_predictions with
  * per_class_proposal=False, lib/ap_helper.py:145-158, and decode_caption, lib/eval_helper.py:46-57; csrc/predictions.hip) --- */

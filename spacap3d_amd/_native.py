@@ -75,6 +75,8 @@ SIGNATURES = {
     "spacap_relation_fused_bwd_sel_f32": (_i, [_p] * 7 + [_i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "spacap_caption_prep_fwd_f32": (_i, [_p] * 7 + [_i] * 5 + [_f, _u64, _p] + [_p] * 7 + [_p]),
     "spacap_caption_prep_bwd_f32": (_i, [_p] * 3 + [_i] * 5 + [_f, _u64, _p, _p, _p, _p]),
+    "spacap_caption_prep_rows_fwd_f32": (_i, [_p] * 6 + [_i] * 7 + [_f, _u64, _p] + [_p] * 2 + [_p]),
+    "spacap_caption_prep_rows_bwd_f32": (_i, [_p] * 3 + [_i] * 7 + [_f, _u64, _p, _p, _p, _p]),
     "spacap_conv1x1_cm_supported": (_i, [_i, _i, _l]),
     "spacap_conv1x1_cm_f32": (_i, [_i, _p, _p, _p, _i, _i, _i, _l, _p, _p]),
     "spacap_sa_l1_stats_f32": (_i, [_p, _p, _p, _p, _p, _i, _f, _i, _i, _i, _i, _i, _p, _p, _p]),
@@ -103,6 +105,7 @@ SIGNATURES = {
                                        _p, _p, _p, _p, ctypes.c_double, _p, _p, _p, _p, _p]),
     "spacap_scst_loss_fwd_f32": (_i, [_p] * 6 + [_i] * 4 + [_p] * 5 + [_p]),
     "spacap_scst_loss_bwd_f32": (_i, [_p] * 7 + [_i] * 3 + [_p, _p]),
+    "spacap_scst_select_f32": (_i, [_p] * 6 + [_i] * 7 + [_f] + [_p] * 6 + [_p]),
     "spacap_dense_caption_select": (_i, [_p] * 5 + [_i] * 5 + [_p] * 7 + [_p]),
     "spacap_multiview_workspace_bytes": (ctypes.c_size_t, [_i]),
     "spacap_multiview_map_f32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, ctypes.c_size_t, _p, _p]),

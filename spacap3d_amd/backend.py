@@ -55,6 +55,7 @@ class HipBackend:
         self.vocab_projection = _lin.vocab_projection
         from . import caption_prep as _cp
         self.caption_prep = _cp.caption_prep
+        self.caption_prep_rows = _cp.caption_prep_rows
         from . import tf_layer as _tf
         self.tf_stack = _tf
         from . import caption_decode as _cd

@@ -68,3 +68,66 @@ def caption_prep(xyz, ref, src, memory, tok, embed, pos):
     x0, mask, idx, dist, good, pred = CaptionPrep.apply(xyz, ref, src, memory, tok, embed.lut.weight, pos.pe[0], p,
                                                         _next_seed() if p > 0.0 else 0)
     return x0, mask, idx, dist, good, pred[0]
+
+
+class CaptionPrepRows(Function):
+    """The decoder input with the proposal given per group: R = B M S rows in B M groups of S; group g of
+    scene g // M reads encoder row ``prop[g]`` of its scene, an empty group (``prop < 0``) zeros.  One launch each way; the
+    backward sums the indicator rows' gradients per (scene, proposal) in ascending (group, sample) order, no atomics."""
+
+    @staticmethod
+    def forward(ctx, src, memory, prop, tok, emb, pe, S, p, seed):
+        dev = src.device
+        B, K, D = src.shape
+        R, T = tok.shape
+        V, S = emb.shape[0], int(S)
+        NG = prop.numel()
+        if S < 1 or NG * S != R or NG % B or prop.dtype != torch.int64:
+            raise RuntimeError(f"caption_prep_rows: {R} token rows at {S} per group need {R // max(S, 1)} int64 proposals, a multiple "
+                               f"of the {B} scenes; got {tuple(prop.shape)} {prop.dtype}")
+        M, L = NG // B, T - 1
+        srcc, prop, tok, embc, pe = src.contiguous(), prop.contiguous(), tok.contiguous(), emb.contiguous(), pe.contiguous()
+        mem = memory.contiguous() if memory is not None else None
+        with torch.cuda.device(dev):
+            x0 = torch.empty(R, L, D, dtype=torch.float32, device=dev)
+            mask = torch.empty(R, L, L, dtype=torch.uint8, device=dev)
+            check(lib.spacap_caption_prep_rows_fwd_f32(srcc.data_ptr(), mem.data_ptr() if mem is not None else None, prop.data_ptr(),
+                                                       tok.data_ptr(), embc.data_ptr(), pe.data_ptr(), B, K, M, S, D, T, V, float(p),
+                                                       int(seed), rng_state(dev).data_ptr(), x0.data_ptr(), mask.data_ptr(),
+                                                       torch.cuda.current_stream(dev).cuda_stream), "spacap_caption_prep_rows_fwd_f32")
+        ctx.save_for_backward(tok, prop)
+        ctx.dims = (B, K, M, S, D, T, V, float(p), int(seed), memory is not None)
+        ctx.mark_non_differentiable(mask)
+        ctx.set_materialize_grads(False)
+        return x0, mask
+
+    @staticmethod
+    def backward(ctx, g, _):
+        tok, prop = ctx.saved_tensors
+        B, K, M, S, D, T, V, p, seed, has_mem = ctx.dims
+        dev = g.device
+        g = g.contiguous()
+        need_rows = ctx.needs_input_grad[0] or (has_mem and ctx.needs_input_grad[1])
+        with torch.cuda.device(dev):
+            d_rows = torch.empty(B, K, D, dtype=torch.float32, device=dev) if need_rows else None
+            d_emb = torch.empty(V, D, dtype=torch.float32, device=dev)
+            check(lib.spacap_caption_prep_rows_bwd_f32(g.data_ptr(), tok.data_ptr(), prop.data_ptr(), B, K, M, S, D, T, V, p, seed,
+                                                       rng_state(dev).data_ptr(), d_rows.data_ptr() if need_rows else None,
+                                                       d_emb.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                  "spacap_caption_prep_rows_bwd_f32")
+        return (d_rows if ctx.needs_input_grad[0] else None, d_rows if (has_mem and ctx.needs_input_grad[1]) else None, None, None,
+                d_emb, None, None, None, None)
+
+
+def caption_prep_rows(src, memory, prop, tok, embed, pos, rows_per_group):
+    """``src`` / ``memory`` (B,K,D) (``memory`` may be None), ``prop`` int64 (B M,) or (B,M) -- the proposal of every group, -1
+    for an empty one --, ``tok`` int64 (B M S, T) in ``lang_label``'s layout with S = ``rows_per_group``; ``embed`` and ``pos`` as
+    ``caption_prep`` takes them.  Returns (x0 (B M S, L, D), mask uint8 (B M S, L, L)), or ``None`` when the op does not apply
+    (the conditions of ``caption_prep``)."""
+    T = tok.shape[1]
+    if not src.is_cuda or src.dtype != torch.float32 or tok.dtype != torch.int64 or T < 2 or pos.pe.shape[1] < T - 2 or \
+            embed.lut.weight.shape[1] != src.shape[-1]:
+        return None
+    p = float(pos.dropout.p) if pos.dropout.training else 0.0
+    return CaptionPrepRows.apply(src, memory, prop.reshape(-1), tok, embed.lut.weight, pos.pe[0], int(rows_per_group), p,
+                                 _next_seed() if p > 0.0 else 0)

@@ -13,6 +13,13 @@
 // Backward: d src = d memory = the indicator row's gradient at (b, idx[b]), zero elsewhere; d E[v] = sum over the positions
 // holding token v, in (scene, position) order, of dropout'(g) * sqrt(D): one workgroup per vocabulary row, no atomics.
 // Dropout is the library's counter hash (dropout.hpp), regenerated in the backward.
+//
+// Row-indexed variant (spacap_caption_prep_rows_*): R rows in NG = B M groups of S; row r belongs to
+// group r / S, the group to scene (r / S) / M, and the group's proposal is prop[group] -- an index per group instead of a
+// nearest centre per row, so that nobody copies the encoder rows M S-fold.  Forward: the indicator row is src[b,k] +
+// memory[b,k] of that proposal (zeros for an empty group, prop outside 0..K-1), the token rows and the mask those of a batch of
+// R rows; no idx / dist / good / pred.  Backward: d_rows[b,k] = the sum of the indicator rows' gradients of the scene's groups
+// that hold k, in ascending (group, sample) order, one thread per element: no atomics, every element written; d E as above.
 #include "common.hpp"
 #include "dropout.hpp"
 
@@ -33,10 +40,14 @@ struct PrepArgs {
   long long *idx;
   float *dist, *pred;
   int *counter;
+  const long long *prop;   // INDEXED: one proposal per group; B is then the number of ROWS, M groups a scene, S rows a group
+  int M, S;
 };
 
 // grid (L, B): block (0, b) finds scene b's proposal and writes the indicator row, the mask and the per-scene scalars; block
 // (row, b) one embedded token row.  Two dependent loads deep at most: the launch is a few microseconds of latency.
+// INDEXED: block (0, r) reads its group's proposal instead of searching for one, and writes no per-scene scalars.
+template <bool INDEXED>
 __global__ __launch_bounds__(256) void cap_prep_fwd_kernel(PrepArgs a) {
   __shared__ float s_d[256];
   __shared__ int s_k[256];
@@ -50,6 +61,24 @@ __global__ __launch_bounds__(256) void cap_prep_fwd_kernel(PrepArgs a) {
       float v = a.emb[(size_t)t * D + c] * a.sqrt_d + a.pe[(size_t)(row - 1) * D + c];
       const bool keep = a.thresh == 0u || hash32((unsigned long long)((size_t)b * L + row) * D + c, sd) >= a.thresh;
       a.x0[((size_t)b * L + row) * D + c] = keep ? v * a.scale : 0.f;
+    }
+    return;
+  }
+  if constexpr (INDEXED) {
+    const int grp = b / a.S, scene = grp / a.M;
+    const long long kp = a.prop[grp];
+    const bool some = kp >= 0 && kp < a.K;
+    for (int c = tid; c < D; c += 256) {
+      float v = 0.f;
+      if (some) {
+        v = a.src[((size_t)scene * a.K + kp) * D + c];
+        if (a.memory) v += a.memory[((size_t)scene * a.K + kp) * D + c];
+      }
+      a.x0[((size_t)b * L) * D + c] = v;
+    }
+    for (int e = tid; e < L * L; e += 256) {
+      const int q = e / L, k = e - q * L;
+      a.mask[(size_t)b * L * L + e] = (a.tok[(size_t)b * a.T + k] > 0 && k <= q) ? 1 : 0;
     }
     return;
   }
@@ -107,8 +136,8 @@ __global__ __launch_bounds__(256) void cap_prep_fwd_kernel(PrepArgs a) {
 
 struct PrepBwdArgs {
   const float *g;
-  const long long *tok, *idx;
-  int B, K, D, T, V, with_rows;
+  const long long *tok, *idx;   // INDEXED: idx = prop [scenes M], B = the number of ROWS
+  int B, K, D, T, V, with_rows, M, S;
   unsigned thresh;
   float scale, sqrt_d;
   unsigned long long seed;
@@ -116,9 +145,44 @@ struct PrepBwdArgs {
   float *d_rows, *d_emb;
 };
 
+template <bool INDEXED>
 __global__ __launch_bounds__(128) void cap_prep_bwd_kernel(PrepBwdArgs a) {
   const int tid = threadIdx.x, L = a.T - 1, D = a.D;
-  if ((int)blockIdx.x >= a.V) {   // 2 048 elements of one scene's (K, D) slab of d src = d memory (was one block per scene: 39 us)
+  if constexpr (INDEXED) {
+    if ((int)blockIdx.x >= a.V) {   // 2 048 elements of one scene's (K, D) slab: each adds up the groups that hold its proposal
+      const int per = (a.K * D + 2047) / 2048, q = blockIdx.x - a.V, b = q / per, e0 = (q - b * per) * 2048;
+      __shared__ int s_prop[128];
+      float acc[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+      for (int m0 = 0; m0 < a.M; m0 += 128) {
+        __syncthreads();
+        if (m0 + tid < a.M) {
+          const long long kp = a.idx[(size_t)b * a.M + m0 + tid];
+          s_prop[tid] = kp >= 0 && kp < a.K ? (int)kp : -1;
+        }
+        __syncthreads();
+        for (int m = 0; m < min(128, a.M - m0); ++m) {
+          const int kp = s_prop[m];
+          if (kp < 0) continue;                         // (uniform over the block)
+          const size_t r0 = ((size_t)b * a.M + m0 + m) * a.S;
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            const int e = e0 + tid + 128 * j;
+            if (e < a.K * D && e / D == kp)
+              for (int s = 0; s < a.S; ++s) acc[j] += a.g[((r0 + s) * L) * D + (e - kp * D)];
+          }
+        }
+      }
+      float *o = a.d_rows + (size_t)b * a.K * D;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int e = e0 + tid + 128 * j;
+        if (e < a.K * D) o[e] = acc[j];
+      }
+      return;
+    }
+  } else if ((int)blockIdx.x >= a.V) {   // 2 048 elements of one scene's (K, D) slab of d src = d memory (was one block per scene: 39 us)
     const int per = (a.K * D + 2047) / 2048, q = blockIdx.x - a.V, b = q / per, e0 = (q - b * per) * 2048;
     const int kb = (int)a.idx[b];
     float *o = a.d_rows + (size_t)b * a.K * D;
@@ -209,11 +273,12 @@ extern "C" int spacap_caption_prep_fwd_f32(const float *xyz, const float *ref, c
   a.sqrt_d = (float)sqrt((double)D);
   a.seed = seed, a.seed_dev = reinterpret_cast<const unsigned long long *>(seed_dev);
   a.x0 = x0, a.mask = mask, a.good = good, a.idx = reinterpret_cast<long long *>(idx), a.dist = dist, a.pred = pred, a.counter = counter;
+  a.prop = nullptr, a.M = a.S = 1;
   SPACAP_REQUIRE(B <= 65535, "%s: B out of range", what);
   // the last-block ticket belongs to THIS call (the caller allocates it with the outputs): launches in flight on other
   // streams, or captured into other graphs, cannot disturb it
   SPACAP_CHECK_HIP(hipMemsetAsync(counter, 0, sizeof(int32_t), spacap::as_stream(stream)), what);
-  hipLaunchKernelGGL(cap_prep_fwd_kernel, dim3(T - 1, B), dim3(256), 0, spacap::as_stream(stream), a);
+  hipLaunchKernelGGL(cap_prep_fwd_kernel<false>, dim3(T - 1, B), dim3(256), 0, spacap::as_stream(stream), a);
   SPACAP_CHECK_LAUNCH(what);
   return SPACAP_OK;
 }
@@ -228,11 +293,56 @@ extern "C" int spacap_caption_prep_bwd_f32(const float *g, const int64_t *tok, c
   SPACAP_REQUIRE(g && tok && idx && d_emb, "%s: null pointer", what);
   SPACAP_REQUIRE(D <= 1024, "%s: D=%d unsupported (at most 1024)", what, D);
   a.g = g, a.tok = reinterpret_cast<const long long *>(tok), a.idx = reinterpret_cast<const long long *>(idx);
-  a.B = B, a.K = K, a.D = D, a.T = T, a.V = V, a.with_rows = d_rows != nullptr;
+  a.B = B, a.K = K, a.D = D, a.T = T, a.V = V, a.with_rows = d_rows != nullptr, a.M = a.S = 1;
   a.sqrt_d = (float)sqrt((double)D);
   a.seed = seed, a.seed_dev = reinterpret_cast<const unsigned long long *>(seed_dev);
   a.d_rows = d_rows, a.d_emb = d_emb;
-  hipLaunchKernelGGL(cap_prep_bwd_kernel, dim3(V + (d_rows ? B * ((K * D + 2047) / 2048) : 0)), dim3(128), 0, spacap::as_stream(stream), a);
+  hipLaunchKernelGGL(cap_prep_bwd_kernel<false>, dim3(V + (d_rows ? B * ((K * D + 2047) / 2048) : 0)), dim3(128), 0, spacap::as_stream(stream), a);
+  SPACAP_CHECK_LAUNCH(what);
+  return SPACAP_OK;
+}
+
+extern "C" int spacap_caption_prep_rows_fwd_f32(const float *src, const float *memory, const int64_t *prop, const int64_t *tok,
+                                                const float *emb, const float *pe, int B, int K, int M, int S, int D, int T, int V,
+                                                float p, uint64_t seed, const uint64_t *seed_dev, float *x0, uint8_t *mask,
+                                                spacap_stream_t stream) {
+  const char *what = "spacap_caption_prep_rows_fwd_f32";
+  PrepArgs a;
+  SPACAP_REQUIRE(B >= 0 && K >= 1 && M >= 1 && S >= 1 && D >= 1 && T >= 2 && V >= 1 && drop_params(p, a.thresh, a.scale),
+                 "%s: bad arguments", what);
+  if (B == 0) return SPACAP_OK;
+  SPACAP_REQUIRE(src && prop && tok && emb && pe && x0 && mask, "%s: null pointer", what);
+  SPACAP_REQUIRE((long long)B * M * S <= 65535, "%s: R = B M S out of range (at most 65535 rows)", what);
+  a.xyz = a.ref = nullptr, a.src = src, a.memory = memory, a.emb = emb, a.pe = pe;
+  a.tok = reinterpret_cast<const long long *>(tok);
+  a.B = B * M * S, a.K = K, a.D = D, a.T = T, a.V = V;
+  a.sqrt_d = (float)sqrt((double)D);
+  a.seed = seed, a.seed_dev = reinterpret_cast<const unsigned long long *>(seed_dev);
+  a.x0 = x0, a.mask = mask, a.good = nullptr, a.idx = nullptr, a.dist = a.pred = nullptr, a.counter = nullptr;
+  a.prop = reinterpret_cast<const long long *>(prop), a.M = M, a.S = S;
+  hipLaunchKernelGGL(cap_prep_fwd_kernel<true>, dim3(T - 1, a.B), dim3(256), 0, spacap::as_stream(stream), a);
+  SPACAP_CHECK_LAUNCH(what);
+  return SPACAP_OK;
+}
+
+extern "C" int spacap_caption_prep_rows_bwd_f32(const float *g, const int64_t *tok, const int64_t *prop, int B, int K, int M, int S,
+                                                int D, int T, int V, float p, uint64_t seed, const uint64_t *seed_dev,
+                                                float *d_rows, float *d_emb, spacap_stream_t stream) {
+  const char *what = "spacap_caption_prep_rows_bwd_f32";
+  PrepBwdArgs a;
+  SPACAP_REQUIRE(B >= 0 && K >= 1 && M >= 1 && S >= 1 && D >= 1 && T >= 2 && V >= 1 && drop_params(p, a.thresh, a.scale),
+                 "%s: bad arguments", what);
+  if (B == 0) return SPACAP_OK;
+  SPACAP_REQUIRE(g && tok && prop && d_emb, "%s: null pointer", what);
+  SPACAP_REQUIRE(D <= 1024, "%s: D=%d unsupported (at most 1024)", what, D);
+  SPACAP_REQUIRE((long long)B * M * S <= 65535, "%s: R = B M S out of range (at most 65535 rows)", what);
+  a.g = g, a.tok = reinterpret_cast<const long long *>(tok), a.idx = reinterpret_cast<const long long *>(prop);
+  a.B = B * M * S, a.K = K, a.D = D, a.T = T, a.V = V, a.with_rows = d_rows != nullptr, a.M = M, a.S = S;
+  a.sqrt_d = (float)sqrt((double)D);
+  a.seed = seed, a.seed_dev = reinterpret_cast<const unsigned long long *>(seed_dev);
+  a.d_rows = d_rows, a.d_emb = d_emb;
+  hipLaunchKernelGGL(cap_prep_bwd_kernel<true>, dim3(V + (d_rows ? B * ((K * D + 2047) / 2048) : 0)), dim3(128), 0,
+                     spacap::as_stream(stream), a);
   SPACAP_CHECK_LAUNCH(what);
   return SPACAP_OK;
 }

@@ -8,8 +8,15 @@ them against the references of the object's corpus key (``rewards``: one launch,
 own samples and leaves the reward-weighted loss (``fused_losses.self_critical_loss``) where the cross-entropy would be.  No
 step reads a value back on the host.
 
+With ``proposals="matched"`` the forward rewards up to ``max_proposals`` annotated objects of every
+scene instead of the batch's one referred object: ``select`` (one launch, csrc/scst_select.hip) pairs every annotated object
+that has references with its nearest proposal and keeps the nearest pairs; the samples, rewards and loss then run over the
+B x ``max_proposals`` groups.
+
 CPU tensors raise ``RuntimeError("... CPU not supported")``: there is no host fallback."""
 import ctypes
+
+import numpy as np
 
 import torch
 
@@ -19,6 +26,9 @@ from .caption_eval import LMAX, MAX_IDS, CaptionCorpus
 from .sampling import check_arguments
 
 BASELINES = ("greedy", "samples")
+PROPOSALS = ("referred", "matched")
+MAX_PROPOSALS = 128        # groups per scene in the matched mode
+MAX_OBJECTS = 256          # object slots per scene spacap_scst_select_f32 takes
 
 
 class SelfCritical:
@@ -28,9 +38,16 @@ class SelfCritical:
     ``num_samples`` = S captions are drawn per scene from softmax(logits / ``temperature``), over the whole vocabulary or the
     ``top_k`` <= 8 most probable words (``sampling.check_arguments``).  ``baseline``: ``"greedy"`` -- the reward of the greedy
     caption of the same proposal -- or ``"samples"`` -- per sample the mean reward of the scene's other samples (S >= 2; no
-    greedy decode runs).  ``seed``: an integer draws the same captions at every call, None new ones per call."""
+    greedy decode runs).  ``seed``: an integer draws the same captions at every call, None new ones per call.
 
-    def __init__(self, corpus, sos, eos, num_samples=5, temperature=1.0, top_k=0, baseline="greedy", seed=None):
+    ``proposals``: ``"referred"`` (the default) rewards the proposal nearest to the batch's referred object and reads neither
+    of the next two arguments.  ``"matched"`` rewards up to ``max_proposals`` = M (1 .. 128) objects per scene: the annotated
+    objects (``box_label_mask`` > 0) with a key row whose nearest proposal lies closer than ``near_threshold`` (> 0; the
+    detector's NEAR_THRESHOLD by default) to their centre, nearest first (``select``).  The batch then carries ``center_label``
+    (B,G,3), ``box_label_mask`` (B,G), ``scene_object_ids`` (B,G) and ``dataset_idx``; ``object_id`` is not read."""
+
+    def __init__(self, corpus, sos, eos, num_samples=5, temperature=1.0, top_k=0, baseline="greedy", seed=None,
+                 proposals="referred", max_proposals=16, near_threshold=0.3):
         if not isinstance(corpus, CaptionCorpus):
             raise TypeError("self_critical: corpus must be a CaptionCorpus")
         if not (0 <= int(sos) < MAX_IDS and 0 <= int(eos) < MAX_IDS):
@@ -47,6 +64,62 @@ class SelfCritical:
         self.baseline = baseline
         self.seed = None if seed is None else int(seed)
         self._df_off = (ctypes.c_int64 * 5)(*[int(x) for x in corpus.df_off])
+        if proposals not in PROPOSALS:
+            raise ValueError(f"self_critical: proposals {proposals!r} unknown (one of {PROPOSALS})")
+        self.proposals = proposals
+        if proposals == "matched":
+            if not 1 <= int(max_proposals) <= MAX_PROPOSALS:
+                raise ValueError(f"self_critical: max_proposals {max_proposals} outside 1 .. {MAX_PROPOSALS}")
+            if not float(near_threshold) > 0.0:
+                raise ValueError(f"self_critical: near_threshold {near_threshold} must be positive")
+            self.max_proposals, self.near_threshold = int(max_proposals), float(near_threshold)
+            self.near2 = float(np.float32(self.near_threshold) * np.float32(self.near_threshold))   # the fp32 product, once
+
+    def select(self, xyz, center_label, box_label_mask, scene_object_ids, dataset_idx, out=None):
+        """The (proposal, object) pairs the matched mode rewards: ``xyz`` (B,K,3) proposal centres, ``center_label`` (B,G,3),
+        ``box_label_mask`` (B,G), ``scene_object_ids`` (B,G), ``dataset_idx`` (B,) or (B,1); G >= ``max_proposals`` = M, G <= 256.
+        Returns ``(prop (B,M) int64, obj (B,M) int64, slot_of (B,M) int32, key (B,M) int32, dist (B,M) float32, n_sel (B,)
+        int32)`` -- per scene the qualifying objects in (distance, slot) order, -1 / +inf in the empty slots --, written into the
+        six tensors of ``out`` when given.  One launch on the current stream, no host synchronisation."""
+        if self.proposals != "matched":
+            raise RuntimeError("self_critical: select() belongs to proposals='matched'")
+        xyz = gpu("self_critical", xyz, "xyz")
+        dev = xyz.device
+        ctr = gpu("self_critical", center_label, "center_label")
+        msk = gpu("self_critical", box_label_mask, "box_label_mask")
+        ids = gpu("self_critical", scene_object_ids, "scene_object_ids")
+        idx = gpu("self_critical", dataset_idx, "dataset_idx").reshape(-1)
+        M = self.max_proposals
+        if xyz.dim() != 3 or xyz.shape[-1] != 3 or ctr.dim() != 3 or ctr.shape[-1] != 3 or ctr.shape[0] != xyz.shape[0] or \
+                tuple(msk.shape) != tuple(ctr.shape[:2]) or tuple(ids.shape) != tuple(ctr.shape[:2]) or idx.numel() != xyz.shape[0]:
+            raise RuntimeError(f"self_critical: expected xyz (B,K,3), center_label (B,G,3), box_label_mask / scene_object_ids (B,G), "
+                               f"dataset_idx (B,); got {tuple(xyz.shape)}, {tuple(ctr.shape)}, {tuple(msk.shape)}, {tuple(ids.shape)}, "
+                               f"{tuple(idx.shape)}")
+        B, K, G = xyz.shape[0], xyz.shape[1], ctr.shape[1]
+        if any(t.device != dev for t in (ctr, msk, ids, idx)):
+            raise RuntimeError(f"self_critical: xyz lives on {dev}, the labels elsewhere")
+        if not (K >= 1 and M <= G <= MAX_OBJECTS):
+            raise RuntimeError(f"self_critical: K={K} proposals, G={G} object slots, max_proposals={M}: supported K >= 1, "
+                               f"max_proposals <= G <= {MAX_OBJECTS}")
+        xyz, ctr, msk = (t.detach().float().contiguous() for t in (xyz, ctr, msk))
+        ids, idx = ids.long().contiguous(), idx.long().contiguous()
+        kt = self.corpus.on(dev)["key_table"]
+        with torch.cuda.device(dev):
+            if out is None:
+                out = (torch.empty(B, M, dtype=torch.int64, device=dev), torch.empty(B, M, dtype=torch.int64, device=dev),
+                       torch.empty(B, M, dtype=torch.int32, device=dev), torch.empty(B, M, dtype=torch.int32, device=dev),
+                       torch.empty(B, M, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+            want = (((B, M), torch.int64), ((B, M), torch.int64), ((B, M), torch.int32), ((B, M), torch.int32),
+                    ((B, M), torch.float32), ((B,), torch.int32))
+            for t, (shape, dtype) in zip(out, want):
+                if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+                    raise RuntimeError(f"self_critical: out must be contiguous {want} on {dev}")
+            prop, obj, slot_of, key, dist, n_sel = out
+            check(lib.spacap_scst_select_f32(xyz.data_ptr(), ctr.data_ptr(), msk.data_ptr(), ids.data_ptr(), idx.data_ptr(),
+                                             kt.data_ptr(), B, K, G, M, kt.shape[0], kt.shape[1], self.corpus.nkeys, self.near2,
+                                             prop.data_ptr(), obj.data_ptr(), slot_of.data_ptr(), key.data_ptr(), dist.data_ptr(),
+                                             n_sel.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "spacap_scst_select_f32")
+        return prop, obj, slot_of, key, dist, n_sel
 
     def rewards(self, tokens, dataset_idx, object_id, rows_per_scene=1, out=None):
         """CIDEr-D of every drawn caption: ``tokens`` (rows, L) decoded words (any integer dtype), row r of scene

@@ -510,6 +510,8 @@ class TransformerDecoderModel(nn.Module):
         teacher-forced pass over the samples and the reward-weighted loss in place of the cross-entropy.  Drawing and scoring run
         under ``no_grad`` through the cached decode kernels (no dropout); only the teacher-forced pass is differentiated.  No
         value is read back on the host."""
+        if sc.proposals == "matched":
+            return self._self_critical_matched(ep, sc, prep, src, memory)
         for k in ("object_id", "dataset_idx"):
             if k not in ep:
                 raise KeyError(f"self_critical: the batch has no {k!r}")
@@ -559,6 +561,65 @@ class TransformerDecoderModel(nn.Module):
         ep["scst_baseline"] = base if base is not None else reward.view(B, S).mean(1)
         ep["scst_advantage"], ep["scst_logp"] = adv.view(B, S), rowlogp.view(B, S)
         ep["scst_sample_scores"], ep["scst_count"] = score, count
+        ep["scst_stats"] = out.detach()
+        return ep
+
+    def _self_critical_matched(self, ep, sc, prep, src, memory):
+        """The same step over every matched object of a scene: ``sc.select`` pairs up to M annotated
+        objects per scene with their nearest proposals, the B M groups play the part the B scenes play above -- S samples, a
+        baseline, S rewards against the object's own references per group; an empty slot draws from a zero indicator and counts
+        for nothing -- and ``caption_prep_rows`` reads the encoder rows by index, so that autograd gets the sum of a proposal's
+        gradients from one launch instead of from M S copies of ``src`` and ``memory``.  No value is read back on the host."""
+        for k in ("center_label", "box_label_mask", "scene_object_ids", "dataset_idx"):
+            if k not in ep:
+                raise KeyError(f"self_critical: the batch has no {k!r}")
+        cd = getattr(ops(), "caption_decode", None)
+        loss_op = getattr(ops(), "self_critical_loss", None)
+        prep_rows = getattr(ops(), "caption_prep_rows", None)
+        te, dec, gen = self.model.tgt_embed, self.model.decoder, self.model.generator
+        B, _, D = src.shape
+        S, M, n_words = sc.num_samples, sc.max_proposals, MAX_DES_LEN + 1
+        dev = src.device
+        with torch.no_grad():
+            # match_idx / pred_ious / good_bbox_masks keep their meaning: the referred object's nearest proposal
+            got = prep(ep["aggregated_vote_xyz"], ep["ref_center_label"], src, memory,
+                       torch.ones(B, 2, dtype=torch.int64, device=dev), te[0], te[1])
+            if got is None or cd is None or loss_op is None or prep_rows is None:
+                raise RuntimeError("self_critical: these tensors are not supported by the fused caption path")
+            _, _, idx, _, good, pred_ious = got
+            prop, obj, _, key, _, _ = sc.select(ep["aggregated_vote_xyz"], ep["center_label"], ep["box_label_mask"],
+                                                ep["scene_object_ids"], ep["dataset_idx"])
+            count = prop >= 0
+            sel = prop.clamp(min=0).unsqueeze(-1).expand(B, M, D)
+            indicator = (src.gather(1, sel) + memory.gather(1, sel)).masked_fill(~count.unsqueeze(-1), 0.0).reshape(B * M, D)
+            if not cd.decode_supported(dec.layers, indicator, n_words):
+                raise RuntimeError("self_critical: this decoder stack is not supported by the fused decode")
+            ys, score, _ = cd.sample_decode(dec, gen, te[0], te[1].pe, indicator, sc.sos, sc.eos, n_words, S, sc.temperature,
+                                            sc.top_k, sc.seed)
+            didx, oid = ep["dataset_idx"].reshape(B, 1).expand(B, M).reshape(-1), obj.reshape(-1)
+            words = ys.view(B * M * S, n_words)
+            reward, _, length, tf_tok = sc.rewards(words, didx, oid, S)
+            base = None
+            if sc.baseline == "greedy":
+                base = sc.rewards(cd.greedy_decode(dec, gen, te[0], te[1].pe, indicator, sc.sos, n_words), didx, oid, 1)[0]
+            tok = torch.cat([torch.ones(B * M * S, 1, dtype=torch.int64, device=dev), tf_tok[:, :-1]], 1)
+        got = prep_rows(src, memory, prop, tok, te[0], te[1], S)
+        if got is None:
+            raise RuntimeError("self_critical: these tensors are not supported by the fused caption path")
+        x0, m8 = got
+        out_full = dec(x0, None, None, m8)
+        vp = getattr(ops(), "vocab_projection", None)
+        logits = vp(out_full, gen.proj, 1) if vp is not None else None
+        if logits is None:
+            logits = gen.proj(out_full[:, 1:, :])
+        out, adv, rowlogp = loss_op(logits, words, length, reward, base, count.reshape(-1), S)
+        ep["_cap_loss"] = (out[0], out[1])
+        ep["match_idx"], ep["pred_ious"], ep["good_bbox_masks"] = idx, pred_ious, good
+        ep["scst_proposal"], ep["scst_object_id"], ep["scst_count"], ep["scst_key"] = prop, obj, count, key
+        ep["scst_samples"], ep["scst_reward"] = ys.view(B, M, S, n_words), reward.view(B, M, S)
+        ep["scst_baseline"] = base.view(B, M) if base is not None else reward.view(B, M, S).mean(2)
+        ep["scst_advantage"], ep["scst_logp"] = adv.view(B, M, S), rowlogp.view(B, M, S)
+        ep["scst_sample_scores"] = score.view(B, M, S)
         ep["scst_stats"] = out.detach()
         return ep
 
