@@ -1116,6 +1116,29 @@ int spacap_caption_reward_f64(const int64_t *tokens, int rows, int rows_per_scen
                               const int64_t *df_off, double log_nkeys, double *cider, int32_t *key, int32_t *length,
                               int64_t *tf_tok, spacap_stream_t stream);
 
+/* Up to three scores per drawn caption and their weighted sum, in the one launch of spacap_caption_reward_f64 (DESIGN.md
+ * section 7l).  Every argument of spacap_caption_reward_f64 means what it means there; spacap_caption_reward_f64 IS this launch
+ * at weights (1, 0, 0).  Per row, against the references of its key row:
+ *   cider f64 [rows]        CIDEr-D, as spacap_caption_reward_f64 writes it, bit for bit;
+ *   bleu4 f64 [rows]        the sentence-level BLEU-4 of the reference's scorer (lib/capeval/bleu/bleu_scorer.py:232-240):
+ *                           prod_{k<4} (correct_k + 1e-15) / (guess_k + 1e-9) to the power 1/4, times exp(1 - 1 / ratio) when
+ *                           ratio = (testlen + 1e-15) / (reflen + 1e-9) < 1; float64;
+ *   rouge f64 [rows]        ROUGE-L F-measure (beta 1.2): the bits spacap_caption_score_f64 writes for this caption as its key's
+ *                           candidate;
+ *   reward f64 [rows]       ((w_cider cider) + (w_bleu bleu4)) + (w_rouge rouge), float64, in that order, un-contracted;
+ *   bleu_comp i32 [rows,10] testlen, closest reflen, guess[4], correct[4], as spacap_caption_score_f64 lays them out.
+ * A term whose weight is exactly 0 is not computed: its output is +0.0 and it adds +0.0 to the reward (bleu_comp holds zeros
+ * when w_bleu is 0).  A row without a key row gets 0 in all four scores, zeros in bleu_comp and key -1.  key, length and tf_tok
+ * as spacap_caption_reward_f64 writes them.  The weights are finite and not negative.  One wave per row, one launch, no atomics,
+ * no state: a captured call replays.  rows = 0 is a no-op. */
+int spacap_caption_reward_mix_f64(const int64_t *tokens, int rows, int rows_per_scene, int L, const int64_t *dataset_idx,
+                                  const int64_t *object_id, const int32_t *key_table, int n_items, int n_obj, int nkeys, int sos,
+                                  int eos, const int32_t *ref_tok, int64_t n_tok, const int32_t *ref_off, const int32_t *ref_len,
+                                  int64_t n_ref, const int32_t *key_ref_off, const uint64_t *df_code, const double *df_idf,
+                                  const int64_t *df_off, double log_nkeys, double w_cider, double w_bleu, double w_rouge,
+                                  double *cider, int32_t *key, int32_t *length, int64_t *tf_tok, double *bleu4, double *rouge,
+                                  double *reward, int32_t *bleu_comp, spacap_stream_t stream);
+
 /* The reward-weighted loss over the drawn words.  logits f32 [R, W, V], words i64 [R, W], length i32 [R] (positions t <
  * length[r] count; clamped to 0..W), reward f64 [R], baseline f64 [R / S] or NULL (leave-one-out: the mean of the scene's
  * other S - 1 rewards; needs S >= 2), count u8 [R / S]; row r = b S + s.
@@ -1132,6 +1155,34 @@ int spacap_scst_loss_fwd_f32(const float *logits, const int64_t *words, const in
                              float *adv, float *rowlogp, float *out, spacap_stream_t stream);
 int spacap_scst_loss_bwd_f32(const float *logits, const int64_t *words, const int32_t *length, const float *pair, const float *adv,
                              const float *out, const float *gloss, int R, int W, int V, float *dlogits, spacap_stream_t stream);
+
+/* Cross-entropy rows and reward rows over ONE logit image.  logits f32 [B0 + R, W, V]: rows 0 .. B0-1
+ * are teacher-forced ground-truth captions, one per scene, with their own W0 <= W word positions (position t >= W0 of such a
+ * row is padding and never counts), target i64 [B0, W0] (row stride tstride >= W0 elements) and good u8 [B0]; rows B0 .. are the R = G S drawn captions of G groups with words i64 [R, W], length i32 [R], reward f64 [R], baseline
+ * f64 [G] or NULL, count u8 [G], exactly as spacap_scst_loss_fwd_f32 takes them.
+ *   L_rl = spacap_scst_loss_fwd_f32's loss over rows B0 .., to the bit;
+ *   L_xe = sum_b good[b] sum_{t < W0: target[b,t] != 0} -logp[b, t, target[b,t]] / (W0 sum_b good[b] + 1e-6), the value
+ *          spacap_cap_loss_fwd_f32 leaves in out[0] for a [B0, W0, V] image: its sum of good runs over the (scene, word) rows
+ *          (a target outside [0, V) is ignored like the pad id 0);
+ *   loss = L_rl + w_xe L_xe  (L_rl itself when B0 = 0 or w_xe = 0).
+ * Forward writes pair f32 [B0 + R, W, 2] = (log-sum-exp, the target's / drawn word's log-probability; zeros at positions that
+ * do not count), hit u8 [B0 + R, W] (workspace), adv f32 [R], rowlogp f32 [R] and
+ *   out f32 [12] = (loss, L_rl, L_xe, share of counted sample positions whose first arg-max is the drawn word, share of counted
+ *                   ground-truth positions whose first arg-max is the target, 1 / (counted sample positions + 1e-6),
+ *                   1 / (W0 good scenes + 1e-6), counting groups, good scenes, mean reward and mean baseline over the counting
+ *                   rows, 0).
+ * No log-probability image; positions that do not count read no logits; the sums run in a fixed order by one wave (bitwise
+ * reproducible).  Two launches.  B0 + R = 0: out zeroed.  With B0 = 0 every output holds spacap_scst_loss_*'s bits.
+ * Backward (one launch over all B0 + R rows): sample rows as spacap_scst_loss_bwd_f32; ground-truth rows
+ * gloss[0] w_xe good[b] out[6] (softmax - onehot) at counted positions; exact zeros everywhere else (every element is written).
+ * w_xe finite and not negative; the same value in both calls. */
+int spacap_mixed_cap_loss_fwd_f32(const float *logits, const int64_t *target, int tstride, const uint8_t *good, int B0, int W0,
+                                  const int64_t *words, const int32_t *length, const double *reward, const double *baseline,
+                                  const uint8_t *count, int R, int S, int W, int V, float w_xe, float *pair, uint8_t *hit, float *adv,
+                                  float *rowlogp, float *out, spacap_stream_t stream);
+int spacap_mixed_cap_loss_bwd_f32(const float *logits, const int64_t *target, int tstride, const uint8_t *good, int B0, int W0,
+                                  const int64_t *words, const int32_t *length, const float *pair, const float *adv, const float *out,
+                                  const float *gloss, int R, int W, int V, float w_xe, float *dlogits, spacap_stream_t stream);
 
 /* The (proposal, object) pairs of a scene that self-critical training rewards (csrc/scst_select.hip).
  * xyz f32 [B,K,3] proposal centres, center_label f32 [B,G,3], box_label_mask f32 [B,G], scene_object_ids i64 [B,G],

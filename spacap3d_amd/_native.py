@@ -103,6 +103,10 @@ SIGNATURES = {
                                       ctypes.c_double, _p, _p, _p, _p]),
     "spacap_caption_reward_f64": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, ctypes.c_int64, _p, _p, ctypes.c_int64,
                                        _p, _p, _p, _p, ctypes.c_double, _p, _p, _p, _p, _p]),
+    "spacap_caption_reward_mix_f64": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, ctypes.c_int64, _p, _p, ctypes.c_int64,
+                                           _p, _p, _p, _p, ctypes.c_double] + [ctypes.c_double] * 3 + [_p] * 8 + [_p]),
+    "spacap_mixed_cap_loss_fwd_f32": (_i, [_p, _p, _i, _p, _i, _i] + [_p] * 5 + [_i] * 4 + [_f] + [_p] * 5 + [_p]),
+    "spacap_mixed_cap_loss_bwd_f32": (_i, [_p, _p, _i, _p, _i, _i] + [_p] * 6 + [_i] * 3 + [_f] + [_p, _p]),
     "spacap_scst_loss_fwd_f32": (_i, [_p] * 6 + [_i] * 4 + [_p] * 5 + [_p]),
     "spacap_scst_loss_bwd_f32": (_i, [_p] * 7 + [_i] * 3 + [_p, _p]),
     "spacap_scst_select_f32": (_i, [_p] * 6 + [_i] * 7 + [_f] + [_p] * 6 + [_p]),

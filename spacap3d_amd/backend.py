@@ -41,6 +41,7 @@ class HipBackend:
         self.relation_losses = _fl.relation_losses
         self.caption_head_loss = _fl.caption_head_loss
         self.self_critical_loss = _fl.self_critical_loss
+        self.mixed_caption_loss = _fl.mixed_caption_loss
         self.loss_tail = _fl.loss_tail
         self.proposal_decode = _fl.proposal_decode
         self.l2norm_rows = _fl.l2norm_rows

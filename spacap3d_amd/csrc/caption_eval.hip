@@ -24,14 +24,14 @@
 // reference's order: bit-equal to Python's.  CIDEr's sums run in wave-reduction order, not the reference's dict order.
 #include <math.h>
 
-#include "cider_common.hpp"
+#include "bleu_rouge_common.hpp"
 
 namespace {
 
 using namespace spacap::eval;
 
-// (CE_LMAX = 64 tokens per sentence = lanes of a wave = bits of the LCS word: cider_common.hpp)
-constexpr double CE_BETA2 = 1.2 * 1.2;              // rouge.py: self.beta ** 2
+// (CE_LMAX = 64 tokens per sentence = lanes of a wave = bits of the LCS word: cider_common.hpp; the closest reference length,
+// the LCS, the clipping and the ROUGE finish: bleu_rouge_common.hpp, shared with caption_reward.hip)
 
 struct SelectArgs {
   const int64_t *tokens;             // [B,K,L]
@@ -120,39 +120,20 @@ __global__ __launch_bounds__(CE_LMAX) void caption_score_kernel(ScoreArgs a) {
   long long r0 = a.refs.key_ref_off[key], r1 = a.refs.key_ref_off[key + 1];
   r0 = r0 < 0 ? 0 : r0;
   r1 = r1 > a.refs.n_ref ? a.refs.n_ref : r1;
-  int best_diff = 0x7fffffff, best_len = 0;
-  double pmax = 0.0, rmax = 0.0;
+  BleuClosest closest;
+  RougeL rl;
   for (long long r = r0; r < r1; ++r) {              // (uniform over the wave)
     uint64_t rc[4];
     const int lr = cider_stage_reference(a.refs, r, lane, s_tok, s_rc, rc);
-
-    // BLEU "closest" reference length: min over (|l - testlen|, l)
-    const int diff = lr > lc ? lr - lc : lc - lr;
-    if (diff < best_diff || (diff == best_diff && lr < best_len)) {
-      best_diff = diff;
-      best_len = lr;
-    }
-
-    // longest common subsequence, bit-parallel over the candidate's positions
-    uint64_t V = ~0ull;
-    for (int i = 0; i < lr; ++i) {
-      const int t = s_tok[i];
-      const uint64_t M = __ballot(lane < lc && ctok == t);
-      const uint64_t U = V & M;
-      V = (V + U) | (V & ~M);
-    }
-    const uint64_t low = lc >= 64 ? ~0ull : ((1ull << lc) - 1ull);
-    const int lcs = __popcll(~V & low);
-    const double prec = (double)lcs / (double)lc, rec = (double)lcs / (double)lr;
-    pmax = prec > pmax ? prec : pmax;
-    rmax = rec > rmax ? rec : rmax;
+    closest.add(lc, lr);
+    rl.add(lcs_bitparallel(s_tok, lr, lc, ctok, lane), lc, lr);
 
     const double penalty = cider_penalty(lc, lr);
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       int cr;
       double val = cider_reference(a.df, s_rc, rc, cc, c, lr, lane, n, cr);
-      if (c.first[n]) maxref[n] = cr > maxref[n] ? cr : maxref[n];
+      bleu_clip_add(c, n, cr, maxref);
       val *= penalty;
       score[n] += val;
     }
@@ -161,19 +142,10 @@ __global__ __launch_bounds__(CE_LMAX) void caption_score_kernel(ScoreArgs a) {
   int correct[4];
 #pragma unroll
   for (int n = 0; n < 4; ++n)
-    correct[n] = spacap::wave_sum(c.first[n] ? (c.count[n] < maxref[n] ? c.count[n] : maxref[n]) : 0);
+    correct[n] = bleu_correct(c, n, maxref);
   if (lane == 0) {
-    int32_t *o = a.bleu + (size_t)key * 10;
-    o[0] = lc;
-    o[1] = best_len;
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      o[2 + n] = lc - n > 0 ? lc - n : 0;
-      o[6 + n] = correct[n];
-    }
-    double rouge = 0.0;
-    if (pmax != 0.0 && rmax != 0.0) rouge = ((1.0 + CE_BETA2) * pmax * rmax) / (rmax + CE_BETA2 * pmax);
-    a.rouge[key] = rouge;
+    bleu_components(lc, closest.best_len, correct, a.bleu + (size_t)key * 10);
+    a.rouge[key] = rl.finish();
     a.cider[key] = cider_finish(score, r1 - r0);
   }
 }

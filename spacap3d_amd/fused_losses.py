@@ -238,6 +238,99 @@ def self_critical_loss(logits, words, length, reward, baseline, count, S):
     return SelfCriticalLoss.apply(logits, words, length, reward, baseline, count, S)
 
 
+class MixedCaptionLoss(Function):
+    """logits (B0 + R, W, V) of ONE teacher-forced pass -- rows 0 .. B0-1 the ground-truth captions, one per scene, rows B0 ..
+    the R = G S drawn captions of G groups -- -> (out (12,), advantage (R,), per-row sum of log-probabilities (R,)): the
+    reward-weighted loss of ``SelfCriticalLoss`` over the sample rows plus ``xe_weight`` times the cross-entropy of
+    ``CaptionHeadLoss`` over the ground-truth rows as two launches forward and one backward
+    (csrc/scst_loss.hip).  ``lang_ids`` (B0, >= W0 + 1) int64 holds the targets from its column 1 on, ``good`` (B0,) which scenes
+    count for the cross-entropy, ``xe_positions`` = W0 <= W the ground-truth rows' own word positions (None: W; positions behind
+    them are padding and never count; the cross-entropy is ``CaptionHeadLoss``'s on a (B0, W0, V) image); the other arguments as
+    ``SelfCriticalLoss`` takes them.
+    out = (loss, L_rl, L_xe, accuracy of the sample rows, accuracy of the ground-truth rows, 1 / (counted sample positions +
+    1e-6), 1 / (W0 good scenes + 1e-6), counting groups, good scenes, mean reward, mean baseline, 0).  No log-probability image is
+    written.  Only ``out[0]`` is differentiable."""
+
+    @staticmethod
+    def forward(ctx, logits, lang_ids, good, words, length, reward, baseline, count, S, xe_weight, xe_positions):
+        if not logits.is_cuda:
+            raise RuntimeError("mixed_caption_loss: CPU not supported")
+        logits = logits.contiguous()
+        N, W, V = logits.shape
+        S, w_xe = int(S), float(xe_weight)
+        dev = logits.device
+        B0 = 0 if lang_ids is None else int(lang_ids.shape[0])
+        R = N - B0
+        W0 = W if xe_positions is None else int(xe_positions)
+        if B0 and not 1 <= W0 <= W:
+            raise RuntimeError(f"mixed_caption_loss: xe_positions {xe_positions} outside 1 .. {W}")
+        if B0:
+            ids = lang_ids.contiguous()
+            g8 = good.to(torch.uint8).contiguous()
+            if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[1] < W0 + 1 or g8.numel() != B0:
+                raise RuntimeError(f"mixed_caption_loss: expected lang_ids ({B0}, >= {W0 + 1}) int64 and good ({B0},); got "
+                                   f"{tuple(ids.shape)} {ids.dtype}, {tuple(g8.shape)}")
+        else:
+            ids = g8 = None
+        words = words.contiguous()
+        length = length.to(torch.int32).contiguous()
+        reward = reward.to(torch.float64).contiguous()
+        base = baseline.to(torch.float64).contiguous() if baseline is not None else None
+        c8 = count.to(torch.uint8).contiguous()
+        if R < 0 or words.dtype != torch.int64 or tuple(words.shape) != (R, W) or length.numel() != R or reward.numel() != R or S < 1 \
+                or R % S or c8.numel() * S != R or (base is not None and base.numel() * S != R):
+            raise RuntimeError(f"mixed_caption_loss: {N} logit rows after {B0} ground-truth rows expect words ({R}, {W}) int64, length "
+                               f"/ reward ({R},), baseline / count ({R}/S,) with S={S}; got {tuple(words.shape)} {words.dtype}, "
+                               f"{tuple(length.shape)}, {tuple(reward.shape)}, {None if base is None else tuple(base.shape)}, "
+                               f"{tuple(c8.shape)}")
+        if not (w_xe >= 0.0 and w_xe != float("inf")):
+            raise ValueError(f"mixed_caption_loss: xe_weight {xe_weight} must be finite and not negative")
+        tstride = ids.shape[1] if B0 else 0
+        with torch.cuda.device(dev):
+            pair = torch.empty(N, W, 2, dtype=torch.float32, device=dev)
+            hit = torch.empty(N, W, dtype=torch.uint8, device=dev)
+            adv = torch.empty(R, dtype=torch.float32, device=dev)
+            rowlogp = torch.empty(R, dtype=torch.float32, device=dev)
+            out = torch.empty(12, dtype=torch.float32, device=dev)
+            # targets = lang_ids[:, 1 : W0 + 1]: same rows, starting one word later
+            check(lib.spacap_mixed_cap_loss_fwd_f32(logits.data_ptr(), ids.data_ptr() + 8 if B0 else None, tstride,
+                                                    g8.data_ptr() if B0 else None, B0, W0, words.data_ptr(), length.data_ptr(),
+                                                    reward.data_ptr(), base.data_ptr() if base is not None else None, c8.data_ptr(),
+                                                    R, S, W, V, w_xe, pair.data_ptr(), hit.data_ptr(), adv.data_ptr(),
+                                                    rowlogp.data_ptr(), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                  "spacap_mixed_cap_loss_fwd_f32")
+        saved = (logits, words, length, pair, adv, out) + ((ids, g8) if B0 else ())
+        ctx.save_for_backward(*saved)
+        ctx.meta = (B0, W0, R, tstride, w_xe)
+        ctx.mark_non_differentiable(adv, rowlogp)
+        ctx.set_materialize_grads(False)
+        return out, adv, rowlogp
+
+    @staticmethod
+    def backward(ctx, g_out, g_adv, g_rowlogp):
+        if g_adv is not None or g_rowlogp is not None:
+            raise RuntimeError("mixed_caption_loss: only the loss (out[0]) is differentiable")
+        B0, W0, R, tstride, w_xe = ctx.meta
+        logits, words, length, pair, adv, out = ctx.saved_tensors[:6]
+        ids, g8 = ctx.saved_tensors[6:] if B0 else (None, None)
+        _, W, V = logits.shape
+        dev = logits.device
+        gl = g_out[0:1].contiguous()
+        with torch.cuda.device(dev):
+            dlogits = torch.empty_like(logits)
+            check(lib.spacap_mixed_cap_loss_bwd_f32(logits.data_ptr(), ids.data_ptr() + 8 if B0 else None, tstride,
+                                                    g8.data_ptr() if B0 else None, B0, W0, words.data_ptr(), length.data_ptr(),
+                                                    pair.data_ptr(), adv.data_ptr(), out.data_ptr(), gl.data_ptr(), R, W, V, w_xe,
+                                                    dlogits.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                  "spacap_mixed_cap_loss_bwd_f32")
+        return (dlogits,) + (None,) * 10
+
+
+def mixed_caption_loss(logits, lang_ids, good, words, length, reward, baseline, count, S, xe_weight, xe_positions=None):
+    """(out (12,), advantage (R,), row log-probabilities (R,)) -- see MixedCaptionLoss."""
+    return MixedCaptionLoss.apply(logits, lang_ids, good, words, length, reward, baseline, count, S, xe_weight, xe_positions)
+
+
 class ProposalDecode(Function):
     """(net (B,CH,K), agg_xyz (B,K,3), mean_size (NS,3)) -> (nt (B,K,CH), center, heading_residuals, size_residuals, bbox_corner
     f64 (B,K,8,3), bbox_mask, sem_cls, size_cls): decode_scores + decode_pred_box (models/proposal_module.py:81-158) as one

@@ -13,6 +13,10 @@ scene instead of the batch's one referred object: ``select`` (one launch, csrc/s
 that has references with its nearest proposal and keeps the nearest pairs; the samples, rewards and loss then run over the
 B x ``max_proposals`` groups.
 
+With ``reward=`` the reward is a weighted sum of CIDEr-D, sentence-level BLEU-4 and ROUGE-L from one launch, and with
+``xe_weight=`` the loss gains the cross-entropy of the referred object's ground-truth caption, from the same teacher-forced
+pass (``tests/reward_mix_restated.py`` restates both).  Both are off by default.
+
 CPU tensors raise ``RuntimeError("... CPU not supported")``: there is no host fallback."""
 import ctypes
 
@@ -29,6 +33,24 @@ BASELINES = ("greedy", "samples")
 PROPOSALS = ("referred", "matched")
 MAX_PROPOSALS = 128        # groups per scene in the matched mode
 MAX_OBJECTS = 256          # object slots per scene spacap_scst_select_f32 takes
+REWARD_TERMS = ("cider", "bleu4", "rouge")   # the columns of the (rows, 3) scores, the order of the reward's sum
+
+
+def reward_weights(reward):
+    """``reward`` -- one of ``REWARD_TERMS`` or a dict over them -- as the three float weights (w_cider, w_bleu, w_rouge)."""
+    if isinstance(reward, str):
+        if reward not in REWARD_TERMS:
+            raise ValueError(f"self_critical: reward {reward!r} unknown (one of {REWARD_TERMS}, or a dict of weights over them)")
+        return tuple(1.0 if k == reward else 0.0 for k in REWARD_TERMS)
+    if not isinstance(reward, dict) or not reward or any(k not in REWARD_TERMS for k in reward):
+        raise ValueError(f"self_critical: reward must be one of {REWARD_TERMS} or a dict of weights over them, got {reward!r}")
+    try:
+        w = tuple(float(reward.get(k, 0.0)) for k in REWARD_TERMS)
+    except (TypeError, ValueError):
+        raise ValueError(f"self_critical: reward weights must be numbers, got {reward!r}") from None
+    if not all(np.isfinite(x) and x >= 0.0 for x in w) or not any(w):
+        raise ValueError(f"self_critical: reward weights must be finite, not negative and not all zero, got {reward!r}")
+    return w
 
 
 class SelfCritical:
@@ -44,10 +66,18 @@ class SelfCritical:
     of the next two arguments.  ``"matched"`` rewards up to ``max_proposals`` = M (1 .. 128) objects per scene: the annotated
     objects (``box_label_mask`` > 0) with a key row whose nearest proposal lies closer than ``near_threshold`` (> 0; the
     detector's NEAR_THRESHOLD by default) to their centre, nearest first (``select``).  The batch then carries ``center_label``
-    (B,G,3), ``box_label_mask`` (B,G), ``scene_object_ids`` (B,G) and ``dataset_idx``; ``object_id`` is not read."""
+    (B,G,3), ``box_label_mask`` (B,G), ``scene_object_ids`` (B,G) and ``dataset_idx``; ``object_id`` is not read.
+
+    ``reward`` and ``xe_weight``.  ``reward``: ``"cider"`` (the default), ``"bleu4"``, ``"rouge"`` or a
+    dict of weights over those three names -- finite, not negative, not all zero --: the reward of a caption is
+    ``w_cider CIDEr-D + w_bleu4 BLEU-4 + w_rouge ROUGE-L`` (sentence-level BLEU-4 and ROUGE-L as the reference's scorers compute
+    them per caption), from one launch.  ``xe_weight`` >= 0: with a positive value the training forward adds ``xe_weight`` times
+    the teacher-forced cross-entropy of the referred object's ground-truth caption (the loss of the plain training forward) to
+    the reward-weighted loss; both come from ONE teacher-forced pass over B + R rows, and the batch then also carries
+    ``lang_label`` and ``lang_ids``.  Anything else raises ``ValueError``."""
 
     def __init__(self, corpus, sos, eos, num_samples=5, temperature=1.0, top_k=0, baseline="greedy", seed=None,
-                 proposals="referred", max_proposals=16, near_threshold=0.3):
+                 proposals="referred", max_proposals=16, near_threshold=0.3, reward="cider", xe_weight=0.0):
         if not isinstance(corpus, CaptionCorpus):
             raise TypeError("self_critical: corpus must be a CaptionCorpus")
         if not (0 <= int(sos) < MAX_IDS and 0 <= int(eos) < MAX_IDS):
@@ -74,6 +104,15 @@ class SelfCritical:
                 raise ValueError(f"self_critical: near_threshold {near_threshold} must be positive")
             self.max_proposals, self.near_threshold = int(max_proposals), float(near_threshold)
             self.near2 = float(np.float32(self.near_threshold) * np.float32(self.near_threshold))   # the fp32 product, once
+        self.reward_weights = reward_weights(reward)
+        try:
+            self.xe_weight = float(xe_weight)
+        except (TypeError, ValueError):
+            raise ValueError(f"self_critical: xe_weight must be a number, got {xe_weight!r}") from None
+        if not (np.isfinite(self.xe_weight) and self.xe_weight >= 0.0):
+            raise ValueError(f"self_critical: xe_weight {xe_weight} must be finite and not negative")
+        # the settings of DESIGN.md section 7l; with the defaults every call goes where it went before them
+        self.mixed = self.reward_weights != (1.0, 0.0, 0.0) or self.xe_weight > 0.0
 
     def select(self, xyz, center_label, box_label_mask, scene_object_ids, dataset_idx, out=None):
         """The (proposal, object) pairs the matched mode rewards: ``xyz`` (B,K,3) proposal centres, ``center_label`` (B,G,3),
@@ -121,12 +160,18 @@ class SelfCritical:
                                              n_sel.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "spacap_scst_select_f32")
         return prop, obj, slot_of, key, dist, n_sel
 
-    def rewards(self, tokens, dataset_idx, object_id, rows_per_scene=1, out=None):
-        """CIDEr-D of every drawn caption: ``tokens`` (rows, L) decoded words (any integer dtype), row r of scene
-        r // ``rows_per_scene``; ``dataset_idx`` and ``object_id`` one entry per scene.  Returns ``(cider (rows,) float64, key
+    def rewards(self, tokens, dataset_idx, object_id, rows_per_scene=1, out=None, terms=False):
+        """The reward of every drawn caption: ``tokens`` (rows, L) decoded words (any integer dtype), row r of scene
+        r // ``rows_per_scene``; ``dataset_idx`` and ``object_id`` one entry per scene.  Returns ``(reward (rows,) float64, key
         (rows,) int32 (-1: the scene has no key row, reward 0), length (rows,) int32, tf_tok (rows, L + 2) int64)``, written into the four
         tensors of ``out`` when given (contiguous, of those shapes and dtypes).  One launch on the current stream, no host
-        synchronisation."""
+        synchronisation.
+
+        The reward is CIDEr-D by default; with the constructor's ``reward`` it is the weighted sum of CIDEr-D, sentence-level
+        BLEU-4 and ROUGE-L (one launch all the same: ``spacap_caption_reward_mix_f64``; a term of weight 0 is not computed and
+        reads 0).  ``terms=True`` returns two more tensors: ``scores (rows, 3) float64`` -- the columns of ``REWARD_TERMS``, a
+        transposed view of a contiguous (3, rows) tensor -- and ``bleu_comp (rows, 10) int32`` (testlen, closest reflen, guess[4],
+        correct[4]; zeros when BLEU-4 has weight 0).  ``out`` then holds six tensors, the fifth the contiguous (3, rows) one."""
         tokens = gpu("self_critical", tokens, "tokens")
         dev = tokens.device
         if tokens.dim() != 2:
@@ -147,19 +192,40 @@ class SelfCritical:
         tokens, idx, oid = (t.long().contiguous() for t in (tokens, idx, oid))
         kt = c["key_table"]
         with torch.cuda.device(dev):
+            n_out = 6 if terms else 4
             if out is None:
                 out = (torch.empty(rows, dtype=torch.float64, device=dev), torch.empty(rows, dtype=torch.int32, device=dev),
                        torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, L + 2, dtype=torch.int64, device=dev))
-            cider, key, length, tf_tok = out
-            want = (((rows,), torch.float64), ((rows,), torch.int32), ((rows,), torch.int32), ((rows, L + 2), torch.int64))
+                if terms:
+                    out += (torch.empty(3, rows, dtype=torch.float64, device=dev), torch.empty(rows, 10, dtype=torch.int32, device=dev))
+            want = (((rows,), torch.float64), ((rows,), torch.int32), ((rows,), torch.int32), ((rows, L + 2), torch.int64),
+                    ((3, rows), torch.float64), ((rows, 10), torch.int32))[:n_out]
+            if len(out) != n_out:
+                raise RuntimeError(f"self_critical: out must hold {n_out} tensors: contiguous {want} on {dev}")
             for t, (shape, dtype) in zip(out, want):
                 if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
                     raise RuntimeError(f"self_critical: out must be contiguous {want} on {dev}")
-            check(lib.spacap_caption_reward_f64(tokens.data_ptr(), rows, rps, L, idx.data_ptr(), oid.data_ptr(), kt.data_ptr(),
-                                                kt.shape[0], kt.shape[1], co.nkeys, self.sos, self.eos, c["ref_tok"].data_ptr(),
-                                                c["ref_tok"].numel(), c["ref_off"].data_ptr(), c["ref_len"].data_ptr(),
-                                                c["ref_len"].numel(), c["key_ref_off"].data_ptr(), c["df_code"].data_ptr(),
-                                                c["df_idf"].data_ptr(), self._df_off, co.log_nkeys, cider.data_ptr(),
-                                                key.data_ptr(), length.data_ptr(), tf_tok.data_ptr(),
-                                                torch.cuda.current_stream(dev).cuda_stream), "spacap_caption_reward_f64")
-        return cider, key, length, tf_tok
+            reward, key, length, tf_tok = out[:4]
+            st = torch.cuda.current_stream(dev).cuda_stream
+            if not terms and self.reward_weights == (1.0, 0.0, 0.0):
+                check(lib.spacap_caption_reward_f64(tokens.data_ptr(), rows, rps, L, idx.data_ptr(), oid.data_ptr(), kt.data_ptr(),
+                                                    kt.shape[0], kt.shape[1], co.nkeys, self.sos, self.eos, c["ref_tok"].data_ptr(),
+                                                    c["ref_tok"].numel(), c["ref_off"].data_ptr(), c["ref_len"].data_ptr(),
+                                                    c["ref_len"].numel(), c["key_ref_off"].data_ptr(), c["df_code"].data_ptr(),
+                                                    c["df_idf"].data_ptr(), self._df_off, co.log_nkeys, reward.data_ptr(),
+                                                    key.data_ptr(), length.data_ptr(), tf_tok.data_ptr(), st), "spacap_caption_reward_f64")
+                return reward, key, length, tf_tok
+            scores, comp = out[4:] if terms else (torch.empty(3, rows, dtype=torch.float64, device=dev),
+                                                  torch.empty(rows, 10, dtype=torch.int32, device=dev))
+            w = self.reward_weights
+            check(lib.spacap_caption_reward_mix_f64(tokens.data_ptr(), rows, rps, L, idx.data_ptr(), oid.data_ptr(), kt.data_ptr(),
+                                                    kt.shape[0], kt.shape[1], co.nkeys, self.sos, self.eos, c["ref_tok"].data_ptr(),
+                                                    c["ref_tok"].numel(), c["ref_off"].data_ptr(), c["ref_len"].data_ptr(),
+                                                    c["ref_len"].numel(), c["key_ref_off"].data_ptr(), c["df_code"].data_ptr(),
+                                                    c["df_idf"].data_ptr(), self._df_off, co.log_nkeys, w[0], w[1], w[2],
+                                                    scores[0].data_ptr(), key.data_ptr(), length.data_ptr(), tf_tok.data_ptr(),
+                                                    scores[1].data_ptr(), scores[2].data_ptr(), reward.data_ptr(), comp.data_ptr(), st),
+                  "spacap_caption_reward_mix_f64")
+        if terms:
+            return reward, key, length, tf_tok, scores.t(), comp
+        return reward, key, length, tf_tok

@@ -509,14 +509,22 @@ class TransformerDecoderModel(nn.Module):
         the referred object's proposal (and, with the greedy baseline, its greedy caption), their CIDEr-D rewards, the
         teacher-forced pass over the samples and the reward-weighted loss in place of the cross-entropy.  Drawing and scoring run
         under ``no_grad`` through the cached decode kernels (no dropout); only the teacher-forced pass is differentiated.  No
-        value is read back on the host."""
+        value is read back on the host.
+
+        With ``sc.reward`` other than CIDEr-D alone the rewards are the weighted sums of the mixed launch
+        and their terms are left as ``scst_reward_terms`` / ``scst_baseline_terms``.  With ``sc.xe_weight`` > 0 the teacher-forced
+        pass runs once over the B ground-truth captions (``lang_label``, at the same proposals) AND the B S samples, and
+        ``mixed_caption_loss`` leaves L_rl + xe_weight L_xe with ``scst_xe_loss`` / ``scst_xe_acc``: one embedding, one vocabulary
+        projection, one loss node -- every parameter keeps one autograd use."""
         if sc.proposals == "matched":
             return self._self_critical_matched(ep, sc, prep, src, memory)
         for k in ("object_id", "dataset_idx"):
             if k not in ep:
                 raise KeyError(f"self_critical: the batch has no {k!r}")
+        xe = sc.xe_weight > 0.0
+        self._scst_xe_keys(ep, xe)
         cd = getattr(ops(), "caption_decode", None)
-        loss_op = getattr(ops(), "self_critical_loss", None)
+        loss_op = getattr(ops(), "mixed_caption_loss" if xe else "self_critical_loss", None)
         te, dec, gen = self.model.tgt_embed, self.model.decoder, self.model.generator
         B, _, D = src.shape
         S, n_words = sc.num_samples, MAX_DES_LEN + 1
@@ -536,15 +544,24 @@ class TransformerDecoderModel(nn.Module):
                                             sc.top_k, sc.seed)
             didx, oid = ep["dataset_idx"].reshape(-1), ep["object_id"].reshape(-1)
             words = ys.view(B * S, n_words)
-            reward, key, length, tf_tok = sc.rewards(words, didx, oid, S)
-            base = None
+            # (with the settings of section 7l the reward and the baseline's reward come from the mixed launch, with their terms)
+            reward, key, length, tf_tok, *terms = sc.rewards(words, didx, oid, S, terms=sc.mixed)
+            base = base_terms = None
             if sc.baseline == "greedy":
-                base = sc.rewards(cd.greedy_decode(dec, gen, te[0], te[1].pe, indicator, sc.sos, n_words), didx, oid, 1)[0]
+                base, _, _, _, *base_terms = sc.rewards(cd.greedy_decode(dec, gen, te[0], te[1].pe, indicator, sc.sos, n_words), didx,
+                                                        oid, 1, terms=sc.mixed)
             count = good & (key.view(B, S)[:, 0] >= 0)
             # the token row caption_prep reads is lang_label's layout: one leading column, then sos and the words (tf_tok is
             # lang_ids' layout); its T = n_words + 2 columns give one logit row per decoded word
             tok = torch.cat([torch.ones(B * S, 1, dtype=torch.int64, device=src.device), tf_tok[:, :-1]], 1)
-        rep = lambda t: t.repeat_interleave(S, 0)      # autograd sums the S gradients of every scene row
+            if xe:
+                gt_tok, tok, loss_words, xe_positions = self._scst_xe_rows(ep, tok, words)
+        if xe:
+            # ONE teacher-forced pass over B ground-truth rows and B S sample rows: every parameter keeps one autograd use
+            rep = lambda t: torch.cat([t, t.repeat_interleave(S, 0)], 0)
+            tok = torch.cat([gt_tok, tok], 0)
+        else:
+            rep = lambda t: t.repeat_interleave(S, 0)      # autograd sums the S gradients of every scene row
         got = prep(rep(ep["aggregated_vote_xyz"]), rep(ep["ref_center_label"]), rep(src), rep(memory), tok, te[0], te[1])
         if got is None:
             raise RuntimeError("self_critical: these tensors are not supported by the fused caption path")
@@ -554,27 +571,70 @@ class TransformerDecoderModel(nn.Module):
         logits = vp(out_full, gen.proj, 1) if vp is not None else None
         if logits is None:
             logits = gen.proj(out_full[:, 1:, :])
-        out, adv, rowlogp = loss_op(logits, words, length, reward, base, count, S)
-        ep["_cap_loss"] = (out[0], out[1])
+        if xe:
+            out, adv, rowlogp = loss_op(logits, ep["lang_ids"], good, loss_words, length, reward, base, count, S, sc.xe_weight,
+                                        xe_positions)
+            ep["_cap_loss"] = (out[0], out[3])
+            ep["scst_xe_loss"], ep["scst_xe_acc"] = out[2].detach(), out[4].detach()
+        else:
+            out, adv, rowlogp = loss_op(logits, words, length, reward, base, count, S)
+            ep["_cap_loss"] = (out[0], out[1])
         ep["match_idx"], ep["pred_ious"], ep["good_bbox_masks"] = idx, pred_ious, good
         ep["scst_samples"], ep["scst_reward"] = ys, reward.view(B, S)
         ep["scst_baseline"] = base if base is not None else reward.view(B, S).mean(1)
         ep["scst_advantage"], ep["scst_logp"] = adv.view(B, S), rowlogp.view(B, S)
         ep["scst_sample_scores"], ep["scst_count"] = score, count
         ep["scst_stats"] = out.detach()
+        if sc.mixed:
+            ep["scst_reward_terms"] = terms[0].view(B, S, 3)
+            ep["scst_baseline_terms"] = base_terms[0] if base_terms is not None else terms[0].view(B, S, 3).mean(1)
         return ep
+
+    @staticmethod
+    def _scst_xe_keys(ep, xe):
+        """With a cross-entropy term the batch carries the referred object's ground-truth caption."""
+        if xe:
+            for k in ("lang_label", "lang_ids", "ref_center_label"):
+                if k not in ep:
+                    raise KeyError(f"self_critical: the batch has no {k!r}")
+
+    @staticmethod
+    def _scst_xe_rows(ep, tok, words):
+        """The rows of the one teacher-forced pass of section 7l at one width: ``lang_label`` (B, Tg) and the samples' token rows
+        ``tok`` (R, Ts) padded with the pad id 0 to T = max(Tg, Ts) columns, and the drawn ``words`` (R, n_words) padded to the
+        W = T - 2 word positions of the pass (behind every row's length: never counted).  The ground-truth rows keep their own
+        Tg - 2 word positions for the loss: what is padded behind them counts for nothing, the denominator included, so the
+        cross-entropy is the plain training forward's.  Returns (ground-truth token rows, sample token rows, words, Tg - 2)."""
+        pad = torch.nn.functional.pad
+        gt, ids = ep["lang_label"], ep["lang_ids"]
+        if gt.dtype != torch.int64 or ids.dtype != torch.int64 or gt.dim() != 2 or ids.dim() != 2 or gt.shape[0] != ids.shape[0]:
+            raise RuntimeError(f"self_critical: lang_label / lang_ids must be int64 (B, T), got {tuple(gt.shape)} {gt.dtype}, "
+                               f"{tuple(ids.shape)} {ids.dtype}")
+        Tg = gt.shape[1]
+        if Tg < 3 or ids.shape[1] < Tg - 1:
+            raise RuntimeError(f"self_critical: lang_label {tuple(gt.shape)} gives {Tg - 2} word positions and needs lang_ids of "
+                               f"{Tg - 1} columns or more, got {tuple(ids.shape)}")
+        T = max(Tg, tok.shape[1])
+        W = T - 2
+        gt = pad(gt, (0, T - Tg)) if Tg < T else gt
+        tok = pad(tok, (0, T - tok.shape[1])) if tok.shape[1] < T else tok
+        words = pad(words, (0, W - words.shape[1])) if words.shape[1] < W else words
+        return gt, tok, words, Tg - 2
 
     def _self_critical_matched(self, ep, sc, prep, src, memory):
         """The same step over every matched object of a scene: ``sc.select`` pairs up to M annotated
         objects per scene with their nearest proposals, the B M groups play the part the B scenes play above -- S samples, a
         baseline, S rewards against the object's own references per group; an empty slot draws from a zero indicator and counts
         for nothing -- and ``caption_prep_rows`` reads the encoder rows by index, so that autograd gets the sum of a proposal's
-        gradients from one launch instead of from M S copies of ``src`` and ``memory``.  No value is read back on the host."""
+        gradients from one launch instead of from M S copies of ``src`` and ``memory``.  No value is read back on the host.
+        ``sc.reward`` and ``sc.xe_weight`` as in ``_self_critical_train``."""
         for k in ("center_label", "box_label_mask", "scene_object_ids", "dataset_idx"):
             if k not in ep:
                 raise KeyError(f"self_critical: the batch has no {k!r}")
+        xe = sc.xe_weight > 0.0
+        self._scst_xe_keys(ep, xe)
         cd = getattr(ops(), "caption_decode", None)
-        loss_op = getattr(ops(), "self_critical_loss", None)
+        loss_op = getattr(ops(), "mixed_caption_loss" if xe else "self_critical_loss", None)
         prep_rows = getattr(ops(), "caption_prep_rows", None)
         te, dec, gen = self.model.tgt_embed, self.model.decoder, self.model.generator
         B, _, D = src.shape
@@ -598,22 +658,48 @@ class TransformerDecoderModel(nn.Module):
                                             sc.top_k, sc.seed)
             didx, oid = ep["dataset_idx"].reshape(B, 1).expand(B, M).reshape(-1), obj.reshape(-1)
             words = ys.view(B * M * S, n_words)
-            reward, _, length, tf_tok = sc.rewards(words, didx, oid, S)
-            base = None
+            reward, _, length, tf_tok, *terms = sc.rewards(words, didx, oid, S, terms=sc.mixed)
+            base = base_terms = None
             if sc.baseline == "greedy":
-                base = sc.rewards(cd.greedy_decode(dec, gen, te[0], te[1].pe, indicator, sc.sos, n_words), didx, oid, 1)[0]
+                base, _, _, _, *base_terms = sc.rewards(cd.greedy_decode(dec, gen, te[0], te[1].pe, indicator, sc.sos, n_words), didx,
+                                                        oid, 1, terms=sc.mixed)
             tok = torch.cat([torch.ones(B * M * S, 1, dtype=torch.int64, device=dev), tf_tok[:, :-1]], 1)
-        got = prep_rows(src, memory, prop, tok, te[0], te[1], S)
+            if xe:
+                # ONE teacher-forced pass over B ground-truth rows and B M S sample rows (every parameter keeps one autograd
+                # use).  caption_prep_rows addresses (scene, proposal) per row and takes its rows scene by scene: with one row per
+                # group, scene b holds its ground-truth row at the referred object's proposal, then its M S sample rows; `first`
+                # then brings the B ground-truth rows to the front, where the loss expects them.
+                gt_tok, tok, loss_words, xe_positions = self._scst_xe_rows(ep, tok, words)
+                T, MS = tok.shape[1], M * S
+                row_prop = torch.cat([idx.view(B, 1), prop.view(B, M, 1).expand(B, M, S).reshape(B, MS)], 1)
+                row_tok = torch.cat([gt_tok.view(B, 1, T), tok.view(B, MS, T)], 1).reshape(B * (1 + MS), T)
+                at = torch.arange(B, device=dev) * (1 + MS)
+                first = torch.cat([at, (at.view(B, 1) + 1 + torch.arange(MS, device=dev).view(1, MS)).reshape(-1)])
+        if xe:
+            got = prep_rows(src, memory, row_prop, row_tok, te[0], te[1], 1)
+        else:
+            got = prep_rows(src, memory, prop, tok, te[0], te[1], S)
         if got is None:
             raise RuntimeError("self_critical: these tensors are not supported by the fused caption path")
         x0, m8 = got
+        if xe:
+            x0, m8 = x0.index_select(0, first), m8.index_select(0, first)
         out_full = dec(x0, None, None, m8)
         vp = getattr(ops(), "vocab_projection", None)
         logits = vp(out_full, gen.proj, 1) if vp is not None else None
         if logits is None:
             logits = gen.proj(out_full[:, 1:, :])
-        out, adv, rowlogp = loss_op(logits, words, length, reward, base, count.reshape(-1), S)
-        ep["_cap_loss"] = (out[0], out[1])
+        if xe:
+            out, adv, rowlogp = loss_op(logits, ep["lang_ids"], good, loss_words, length, reward, base, count.reshape(-1), S,
+                                        sc.xe_weight, xe_positions)
+            ep["_cap_loss"] = (out[0], out[3])
+            ep["scst_xe_loss"], ep["scst_xe_acc"] = out[2].detach(), out[4].detach()
+        else:
+            out, adv, rowlogp = loss_op(logits, words, length, reward, base, count.reshape(-1), S)
+            ep["_cap_loss"] = (out[0], out[1])
+        if sc.mixed:
+            ep["scst_reward_terms"] = terms[0].view(B, M, S, 3)
+            ep["scst_baseline_terms"] = base_terms[0].view(B, M, 3) if base_terms is not None else terms[0].view(B, M, S, 3).mean(2)
         ep["match_idx"], ep["pred_ious"], ep["good_bbox_masks"] = idx, pred_ious, good
         ep["scst_proposal"], ep["scst_object_id"], ep["scst_count"], ep["scst_key"] = prop, obj, count, key
         ep["scst_samples"], ep["scst_reward"] = ys.view(B, M, S, n_words), reward.view(B, M, S)
