@@ -708,7 +708,9 @@ int spacap_dense_wgrad_small_f32(const float *G, long ldg, const float *X, long 
                                  int M, int N, float *dW, float *db, spacap_stream_t stream);
 /* Block-diagonal weight gradient dW[o][z N + n] = sum_r G[r][z M + o] X[r][z N + n], z < Z (the relation head's first Linear
    applied per head, models/transformer_captioner.py:319-326): part f32 [nslab][M][Z N] per-row-slab partials in dW's layout,
-   nslab = spacap_dense_wgrad_blocks_slabs(R) or any count >= 1; the caller adds the slabs in order. */
+   nslab = spacap_dense_wgrad_blocks_slabs(R) or any count in 1 .. 65535 (as for the tall gradient below); the caller adds the
+   slabs in order.  Slab s covers the rows [s per, min(R, (s + 1) per)), per = ceil(R / nslab); a slab without rows is written
+   as zeros.  A non-finite X[r][z N + n] reaches only the elements (., z N + n) of its row's slab. */
 int spacap_dense_wgrad_blocks_slabs(long R);
 int spacap_dense_wgrad_blocks_f32(const float *G, long ldg, const float *X, long ldx, long R, int Z, int M, int N, int nslab,
                                   float *part, spacap_stream_t stream);

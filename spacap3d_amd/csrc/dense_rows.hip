@@ -394,11 +394,14 @@ __global__ __launch_bounds__(256) void dense_wgrad_blocks_kernel(const float *__
         float g[8], xv[8][8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const long r = rr + j < rend ? rr + j : rend - 1;
-          g[j] = rr + j < rend ? G[(size_t)r * ldg + (size_t)z * M + o] : 0.f;
+          // rows past the slab: both operands zero (the address stays on the slab's last row; its X may hold an Inf, and
+          // 0 * Inf would put a NaN into every sum of the column)
+          const bool rok = rr + j < rend;
+          const long r = rok ? rr + j : rend - 1;
+          g[j] = rok ? G[(size_t)r * ldg + (size_t)z * M + o] : 0.f;
           const float *x = X + (size_t)r * ldx + (size_t)z * N + n0;
 #pragma unroll
-          for (int u = 0; u < 8; ++u) xv[j][u] = n0 + u < N ? x[u] : 0.f;
+          for (int u = 0; u < 8; ++u) xv[j][u] = (rok && n0 + u < N) ? x[u] : 0.f;
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j)
@@ -421,11 +424,13 @@ extern "C" int spacap_dense_wgrad_blocks_slabs(long R) {
 }
 
 /* part f32 [nslab][M][Z N]: per row slab, dW[o][z N + n] = sum_r G[r][z M + o] X[r][z N + n] (block-diagonal product of G^T X);
-   G rows of Z M floats at stride ldg, X rows of Z N floats at stride ldx.  The caller adds the slabs in order. */
+   G rows of Z M floats at stride ldg, X rows of Z N floats at stride ldx; nslab in 1 .. 65535, a slab without rows is zeros.
+   The caller adds the slabs in order. */
 extern "C" int spacap_dense_wgrad_blocks_f32(const float *G, long ldg, const float *X, long ldx, long R, int Z, int M, int N, int nslab,
                                              float *part, spacap_stream_t stream) {
   const char *what = "spacap_dense_wgrad_blocks_f32";
-  SPACAP_REQUIRE(R >= 1 && Z >= 1 && Z <= 65535 && M >= 1 && N >= 1 && nslab >= 1 && ldg >= (long)Z * M && ldx >= (long)Z * N,
+  SPACAP_REQUIRE(R >= 1 && Z >= 1 && Z <= 65535 && M >= 1 && N >= 1 && nslab >= 1 && nslab <= 65535 && ldg >= (long)Z * M &&
+                     ldx >= (long)Z * N,
                  "%s: bad sizes", what);
   SPACAP_REQUIRE(G && X && part, "%s: null pointer", what);
   hipLaunchKernelGGL(dense_wgrad_blocks_kernel, dim3(nslab, Z), dim3(256), 0, spacap::as_stream(stream), G, ldg, X, ldx, R, Z, M, N, part);
