@@ -601,6 +601,47 @@ int spacap_adam_flat_f32(float *p, const float *g, float *m, float *v, long n, f
                          float eps, float weight_decay, const float *step, float grad_scale,
                          const int64_t *skip_if_nonzero, spacap_stream_t stream);
 
+/* ---- optimizer, second mode: parameter groups + global-norm clipping + non-finite skip (csrc/optim.hip) ----------
+ * torch.optim.Adam([{non-caption}, {caption, lr: transformer_lr}], lr, weight_decay) (scripts/train.py:226-236) with
+ * torch.nn.utils.clip_grad_norm_, as three stream-ordered, capturable launches; none reads the host or allocates.
+ * Segment table (one entry per bucket parameter, sorted): seg_off i64 [S+1] in elements, seg_off[0] = 0, seg_off[S] = n,
+ * every entry but the last a multiple of 4; seg_group i32 [S] in [0, G).  G <= 8, S <= 4096.  The device copies are what
+ * the kernels read; the *_host copies (nullable) are checked by the entry point.  Padding elements are zero and belong
+ * to the segment before them.
+ * ctrl f32 [SPACAP_OPTIM_CTRL_FLOATS], the control record: [COEF] clip coefficient min(1, max_norm / (norm + 1e-6)),
+ * computed in double, rounded once (1 when [MAX_NORM] <= 0); [APPLY] 1 or 0; [STEP] Adam's 1-based step count, advanced by
+ * spacap_optim_finish_f64 only when the update is applied; [MAX_NORM] INPUT, written by the host; [NORM] the pre-clip norm
+ * of the mean gradient grad_scale * sqrt(sq[G]); [GROUP_NORM + k] the same per group. */
+#define SPACAP_OPTIM_MAX_GROUPS 8
+#define SPACAP_OPTIM_MAX_SEGMENTS 4096
+#define SPACAP_OPTIM_CTRL_COEF 0
+#define SPACAP_OPTIM_CTRL_APPLY 1
+#define SPACAP_OPTIM_CTRL_STEP 2
+#define SPACAP_OPTIM_CTRL_MAX_NORM 3
+#define SPACAP_OPTIM_CTRL_NORM 4
+#define SPACAP_OPTIM_CTRL_GROUP_NORM 5
+#define SPACAP_OPTIM_CTRL_FLOATS 16
+/* workgroups of the norm pass over n elements = rows of its partials buffer */
+int spacap_optim_blocks(long n);
+/* partials f64 [spacap_optim_blocks(n)][G]: sums of (double)g * (double)g, each workgroup in its own slots, every slot
+ * written; bit-reproducible from run to run (no floating-point atomics, one fixed summation order). */
+int spacap_grad_sqnorm_f32(const float *g, long n, const int64_t *seg_off, const int32_t *seg_group, int S, int G,
+                           const int64_t *seg_off_host, const int32_t *seg_group_host, double *partials,
+                           spacap_stream_t stream);
+/* One workgroup: sq f64 [G+1] = the partials summed in a fixed order (last entry: the total), then the control record.
+ * APPLY is 0 when the total is not finite or *skip_if_nonzero (nullable) is set; STEP += 1 only when APPLY, otherwise
+ * skipped i64 [1] += 1.  A skipped update is not terminal: p, m, v and the step count stay exactly as they were. */
+int spacap_optim_finish_f64(const double *partials, int blocks, int G, float grad_scale, const int64_t *skip_if_nonzero,
+                            double *sq, float *ctrl, int64_t *skipped, spacap_stream_t stream);
+/* spacap_adam_flat_f32's update with lr / weight_decay per group from hyper f32 [G][2], the gradient scale
+ * grad_scale * ctrl[COEF] (formed once per thread in f32), t = ctrl[STEP]; returns at once when ctrl[APPLY] == 0.  Same
+ * expression order: one group, equal hyper-parameters and COEF == 1 give spacap_adam_flat_f32's result bit for bit.
+ * n must be a multiple of 4 (the bucket pads every tensor to 16 bytes). */
+int spacap_adam_flat_groups_f32(float *p, const float *g, float *m, float *v, long n, const int64_t *seg_off,
+                                const int32_t *seg_group, int S, int G, const int64_t *seg_off_host,
+                                const int32_t *seg_group_host, const float *hyper, float beta1, float beta2, float eps,
+                                const float *ctrl, float grad_scale, spacap_stream_t stream);
+
 /* ---- detection losses of the training step (csrc/losses.hip) ----------------------------------------------------
  * Replaces compute_vote_loss / compute_objectness_loss / compute_box_and_sem_cls_loss (lib/loss_helper.py:35-197,
  * utils/nn_distance.py:32-62).  net f32 [B,K,CH] = the proposal head's output rows [objectness 2 | centre offset 3 |

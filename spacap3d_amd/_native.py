@@ -203,7 +203,11 @@ SIGNATURES = {
     "spacap_sum_slabs_f32": (_i, [_p, _i, _l, _p, _p]),
     "spacap_sum_slabs_batched_f32": (_i, [_p, _p, _p, _p, _i, _p]),
     "spacap_adam_flat_f32": (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _p, _f, _p, _p]),
-    "spacap_linear_dgrad_mask_f32": (_i, [_p, _p, _p, _f, _l, _i, _i, _p, _p]),
+    "spacap_optim_blocks": (_i, [_l]),
+    "spacap_grad_sqnorm_f32": (_i, [_p, _l, _p, _p, _i, _i, _p, _p, _p, _p]),
+    "spacap_optim_finish_f64": (_i, [_p, _i, _i, _f, _p, _p, _p, _p, _p]),
+    "spacap_adam_flat_groups_f32": (_i, [_p, _p, _p, _p, _l, _p, _p, _i, _i, _p, _p, _p, _f, _f, _f, _p, _f, _p]),
+    "spacap_linear_dgrad_mask_f32":(_i, [_p, _p, _p, _f, _l, _i, _i, _p, _p]),
     "spacap_rel_tail_fwd_f32": (_i, [_p, _p, _p, _p, _p, _l, _p, _p, _p]),
     "spacap_rel_tail_bwd_nparts": (_i, [_l]),
     "spacap_rel_tail_bwd_f32": (_i, [_p, _p, _p, _l, _p, _p, _p]),

@@ -33,11 +33,17 @@ def _role_stream(device, role):
 class Trainer:
     def __init__(self, model: torch.nn.Module, mean_size_arr, lr: float = 1e-3, weight_decay: float = 1e-5,
                  use_relation: bool = True, split_optimizer: bool = False,
-                 adam_eps: float = 1e-8):
+                 adam_eps: float = 1e-8, transformer_lr: float = None, max_grad_norm: float = None):
         self.model = model
         self.mean_size_arr = mean_size_arr
         self.use_relation = use_relation
         self.lr, self.weight_decay, self.adam_eps = lr, weight_decay, adam_eps
+        # Either one switches the optimizer to its grouped mode (optim.FlatAdam): the reference's two
+        # parameter groups ("caption" in the name: transformer_lr; scripts/train.py:226-236), gradient clipping by the global
+        # norm on the device, and rates that live in device memory.  Both None: the one-launch optimizer, as before.
+        self.transformer_lr, self.max_grad_norm = transformer_lr, max_grad_norm
+        self.grouped = transformer_lr is not None or max_grad_norm is not None
+        self._pending_optimizer_state = None    # load_optimizer_state_dict before the first step: applied by _setup
         self.bucket = None
         self.optimizer = None
         self.side_stream = None
@@ -235,11 +241,21 @@ class Trainer:
         kw = dict(lr=self.lr, weight_decay=self.weight_decay, eps=self.adam_eps)
         if used[0].is_cuda:
             from .optim import FlatAdam   # one launch over a flat parameter buffer (spacap3d_amd/optim.py)
+            if self.grouped:
+                kw.update(groups=self._reference_groups(), max_grad_norm=self.max_grad_norm)
             self.optimizer = FlatAdam(self.bucket, **kw)
             self._attach_packed_qkv()
             self._register_grad_slots()
+        elif self.grouped:
+            # (the CPU checker: torch's own optimizer over the same two groups, restricted to the parameters with gradients)
+            inside = {id(p) for p in used}
+            dicts = [dict(g, params=[p for p in g["params"] if id(p) in inside]) for g in self._reference_groups()]
+            self.optimizer = torch.optim.Adam(dicts, **kw)
         else:
             self.optimizer = torch.optim.Adam(used, **kw)
+        if self._pending_optimizer_state is not None:
+            sd, self._pending_optimizer_state = self._pending_optimizer_state, None
+            self.load_optimizer_state_dict(sd)
         self._find_captioner_suffix()
         if used[0].is_cuda and self._sig is None:
             # here and not at first use: a zero-fill issued inside enable_graph's capture would be replayed every step
@@ -248,6 +264,45 @@ class Trainer:
             self._one = torch.ones_like(d["loss"].detach())
             self._comm_stream = _role_stream(used[0].device, "comm")
             self._err_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+
+    # -- the reference's optimizer layout: groups, checkpoints -----------------------------------------------------------
+    def _reference_groups(self):
+        """Group 0: every ``requires_grad`` parameter without "caption" in its name, group 1: those with, both in
+        ``named_parameters()`` order and INCLUDING the ones the loss never reaches (they hold no state, but they count in the
+        reference optimizer's numbering).  Either group may be empty (a ``no_caption`` model, a frozen detector)."""
+        from .optim import reference_groups
+        return reference_groups(self.model, self.lr, self.transformer_lr)
+
+    def _flat_optimizer(self, what):
+        if self.optimizer is None:
+            raise RuntimeError(f"Trainer.{what}: no optimizer yet -- it is built from the first batch: call step() or "
+                               "enable_graph() first")
+        if isinstance(self.optimizer, torch.optim.Optimizer):
+            raise RuntimeError(f"Trainer.{what}: CPU not supported")
+        return self.optimizer
+
+    def optimizer_state_dict(self):
+        """``optimizer.state_dict()`` as the reference's Solver checkpoints it (lib/solver.py:216-225), indexed as the
+        reference's optimizer is (see _reference_groups), in both optimizer modes.  Reads the step count from the device."""
+        return self._flat_optimizer("optimizer_state_dict").state_dict(self._reference_groups())
+
+    def load_optimizer_state_dict(self, sd):
+        """The ``optimizer_state_dict`` entry of a reference ``model_last.pth`` (or of optimizer_state_dict()), as it is:
+        moments, step count, rates and weight decay.  Before the first step the dict is kept and applied as soon as the
+        optimizer exists (the parameter bucket is laid out from the first batch).  Under an active graph nothing is
+        re-captured in the grouped mode: the state and the rates live in the buffers the graph reads; in the ungrouped
+        mode a changed rate re-captures, as set_hyper does."""
+        if self.optimizer is None:
+            self._pending_optimizer_state = sd
+            return
+        opt = self._flat_optimizer("load_optimizer_state_dict")
+        before = (opt.lr, opt.weight_decay)
+        opt.load_state_dict(sd, self._reference_groups())
+        self.lr = opt.lr
+        if opt.grouped:
+            self.transformer_lr = opt.param_groups[1]["lr"]
+        elif self.graph is not None and (opt.lr, opt.weight_decay) != before:
+            self._recapture = True
 
     def _adopt_bn_counters(self):
         """The ``num_batches_tracked`` buffers of the BatchNorm layers whose training forward runs through the fused ops
@@ -389,6 +444,10 @@ class Trainer:
         # the loss terms of this step as device scalars (no host sync; under graph replay: the static result tensors)
         self.last_losses = {k: d[k].detach() for k in ("loss", "vote_loss", "objectness_loss", "box_loss", "sem_cls_loss",
                                                        "cap_loss", "relation_loss") if k in d and torch.is_tensor(d[k])}
+        if getattr(self.optimizer, "grouped", False):
+            # the optimizer's telemetry (static device scalars, rewritten by every update; no host read)
+            self.last_losses.update(grad_norm=self.optimizer.grad_norm, clip_coef=self.optimizer.clip_coef,
+                                    skipped_updates=self.optimizer.skipped_updates)
         return d["loss"].detach()
 
     def _seed_grad(self, loss):
@@ -422,6 +481,8 @@ class Trainer:
         if flat:
             self.optimizer.step(grad_scale=scale)
         else:
+            if self.max_grad_norm is not None:
+                torch.nn.utils.clip_grad_norm_([p for p in self.bucket.params if p.grad is not None], self.max_grad_norm)
             self.optimizer.step()
 
     # -- all-reduce overlapped with the backward ---------------------------------------------------------------------
@@ -622,11 +683,38 @@ class Trainer:
         self._graph_grads = [p.grad for p in self.bucket.params]
         self._recapture = False
 
-    def set_hyper(self, lr=None, bn_momentum=None):
+    def set_hyper(self, lr=None, bn_momentum=None, transformer_lr=None):
         """Change the learning rate and / or the BatchNorm momentum (what the reference's Solver does every epoch with
         StepLR / BNMomentumScheduler, lib/solver.py:228-235).  These scalars are kernel ARGUMENTS, i.e. frozen into a
         captured hipGraph: when a graph is active it is re-captured (same static buffers, no warm-up steps) at the
-        next step."""
+        next step.
+
+        Grouped optimizer (``transformer_lr`` / ``max_grad_norm`` given at construction): the rates live in device memory, a
+        change is one stream-ordered copy and the graph stays as it is; only ``bn_momentum`` still re-captures.  ``lr`` is
+        the first group's rate there, ``transformer_lr`` the captioner's."""
+        if transformer_lr is not None and not self.grouped:
+            raise ValueError("Trainer.set_hyper: transformer_lr needs a Trainer built with transformer_lr= or max_grad_norm=")
+        if self.grouped:
+            if lr is not None:
+                self.lr = float(lr)
+            if transformer_lr is not None:
+                self.transformer_lr = float(transformer_lr)
+            rates = [self.lr if lr is not None else None, self.transformer_lr if transformer_lr is not None else None]
+            if lr is not None and self.transformer_lr is None:
+                rates[1] = self.lr      # (no rate of its own: the captioner follows lr, as at construction)
+            if isinstance(self.optimizer, torch.optim.Optimizer):
+                for grp, x in zip(self.optimizer.param_groups, rates):
+                    if x is not None:
+                        grp["lr"] = x
+            elif self.optimizer is not None and (lr is not None or transformer_lr is not None):
+                self.optimizer.set_lr(group_lrs=rates)
+            if bn_momentum is not None:
+                for m in self.model.modules():
+                    if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
+                        m.momentum = float(bn_momentum)
+                if self.graph is not None:
+                    self._recapture = True
+            return
         if lr is not None:
             self.lr = float(lr)
             if isinstance(self.optimizer, torch.optim.Optimizer):
