@@ -981,6 +981,22 @@ int spacap_sample_word_f32(const float *x, const void *Wp, const float *bias, lo
                            const uint64_t *seed_dev, int n_words, int step, int eos, const float *lut, float scale, const float *pe_row,
                            int64_t *ys, float *score, int32_t *length, int32_t *finished, float *xw, void *workspace,
                            spacap_stream_t stream);
+/* Nucleus (top-p) sampling ("Top-p", restated by tests/nucleus_restated.py): the step above with the draw
+ * restricted to the row's nucleus.  With l the row's logits (spacap_decode_word_f32's, bit for bit), q = softmax(l * inv_tau)
+ * and A_v = sum of q_u over the words u with l_u > l_v (the mass strictly more probable than v), the nucleus is
+ * { v : A_v < top_p }: words with equal logits enter or stay out together, the most probable word is always in, and no sort
+ * order is involved.  The row draws the first maximum over the nucleus of z_v = l_v * inv_tau + g_v, g as above with the same
+ * flat index, so a row whose unrestricted draw (top_k = 0) lies in its nucleus draws that same word.  logp, the row state, ys
+ * and xw are as for spacap_sample_word_f32.  0 < top_p <= 1, finite (at 1 a word stays out only when the float32 mass above it
+ * rounds to the whole sum); inv_tau finite and > 0; 0 <= eos < V; 1 <= V <= 16 384 (a row sits in LDS, 8 bytes a word).
+ * This mode alone writes the logits to device memory: workspace = spacap_sample_word_nucleus_workspace_bytes(rows, V) bytes
+ * = rows * (V rounded up to a multiple of 64) * 4, 16-byte aligned, holds them between its two launches.  Sums run in a
+ * fixed order without atomics: the same inputs give the same words on every call.  No host read; graph-capturable. */
+size_t spacap_sample_word_nucleus_workspace_bytes(long rows, int V);
+int spacap_sample_word_nucleus_f32(const float *x, const void *Wp, const float *bias, long rows, int V, float top_p, float inv_tau,
+                                   uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos, const float *lut, float scale,
+                                   const float *pe_row, int64_t *ys, float *score, int32_t *length, int32_t *finished, float *xw,
+                                   void *workspace, spacap_stream_t stream);
 /* Split-K product for the skinny feed-forward products (K = d_ff, N = 128: w_2 forward, the data gradient through w_1):
  * out[s][r][n] = sum_{k in slice s} a[r][k] Wop[k][n], Wop[k][n] = trans_w ? W[n][k] (W [N,K]) : W[k][n] (W [K,N]);
  * a [R,K], K and N multiples of 128, nsplit a divisor of K / 128 (spacap_tf_gemm_splits suggests the one that fills the

@@ -247,6 +247,8 @@ SIGNATURES = {
     "spacap_beam_finish_f32": (_i, [_p, _p, _p, _p, _l, _i, _i, ctypes.c_double, _p, _p, _p, _p, _p, _p]),
     "spacap_sample_word_workspace_bytes": (ctypes.c_size_t, [_l, _i, _i]),
     "spacap_sample_word_f32": (_i, [_p, _p, _p, _l, _i, _i, _f, _u64, _p, _i, _i, _i, _p, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "spacap_sample_word_nucleus_workspace_bytes": (ctypes.c_size_t, [_l, _i]),
+    "spacap_sample_word_nucleus_f32": (_i, [_p, _p, _p, _l, _i, _f, _f, _u64, _p, _i, _i, _i, _p, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
     "spacap_tf_gemm_splits": (_i, [_l, _i, _i]),
     "spacap_tf_gemm_f32": (_i, [_p, _p, _l, _i, _i, _i, _i, _p, _p]),
     "spacap_tf_dgrad_mask_f32": (_i, [_p, _p, _p, _f, _l, _i, _i, _p, _p]),

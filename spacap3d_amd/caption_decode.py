@@ -216,8 +216,12 @@ def beam_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, beam_si
     return (ys, best, beams, scores, lengths) if return_all else (ys, best)
 
 
+NUCLEUS_MAX_V = 16384     # spacap_sample_word_nucleus_f32 keeps a row in LDS, 8 bytes a word
+
+
 @torch.no_grad()
-def sample_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, num_samples=1, temperature=1.0, top_k=0, seed=None):
+def sample_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, num_samples=1, temperature=1.0, top_k=0, seed=None,
+                  top_p=None):
     """Sampled decoding of R sequences, ``num_samples`` = S captions each (the reference decodes greedily
     only): the ``greedy_decode`` loop at R S rows (row r S + s = sample s of sequence r; rows are independent, so the attention is
     the greedy one and there is no ancestor table) with ``spacap_sample_word_f32`` as the word choice: the Gumbel-max draw from
@@ -226,15 +230,23 @@ def sample_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, num_s
     ``seed``: an integer draws the same captions at every call; None takes the host word from ``attention._next_seed()`` and
     mixes in the device word ``attention.rng_state``, so a captured graph draws new captions after every ``advance_rng``.  No step
     reads a value back on the host.  Cache memory: 12 R S T 512 bytes for 6 layers.
+    ``top_p`` in (0, 1): nucleus sampling instead (``spacap_sample_word_nucleus_f32``; the semantics are stated in
+    ``sampling.py``) -- the draw is restricted to the words whose strictly more probable words hold less than ``top_p`` of the
+    tempered distribution.  This mode alone keeps a step's logits in HBM, R S x (V rounded up to 64) floats, between its two
+    launches.  None or 1.0 is the path above, bit for bit; ``top_p`` < 1 with ``top_k`` >= 1 is refused: one restriction at a time.
     Returns ``(ys (R, S, n_words) int64, score (R, S) float32, length (R, S) int32)``: the words (eos repeats after the first
-    eos), the summed log-probabilities through the first eos, and the position of the first eos plus one (``n_words``: none)."""
+    eos), the summed log-probabilities through the first eos, and the position of the first eos plus one (``n_words``: none);
+    or None -- not taken -- for nucleus sampling over more than ``NUCLEUS_MAX_V`` words."""
     from .attention import _next_seed, rng_state
-    from .sampling import check_arguments
+    from .sampling import check_arguments, nucleus_of
     R, dev = indicator.shape[0], indicator.device
     S, k, tau = int(num_samples), int(top_k), float(temperature)
     T = n_words + 1
     V = generator.proj.weight.shape[0]
-    check_arguments("sample_decode", S, tau, k, V)
+    check_arguments("sample_decode", S, tau, k, V, top_p)
+    p = nucleus_of(top_p)
+    if p is not None and V > NUCLEUS_MAX_V:
+        return None
     RS = R * S
     s = _Stack(dec, generator, embed, pe, RS, T, dev)
     st = s.st
@@ -257,7 +269,8 @@ def sample_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, num_s
 
         x = indicator.contiguous().repeat_interleave(S, 0) if S > 1 else indicator.contiguous()
         s.allocate(on_cache_oom=cache_oom)
-        ws = torch.empty(int(lib.spacap_sample_word_workspace_bytes(RS, V, k)), dtype=torch.uint8, device=dev)
+        need = lib.spacap_sample_word_workspace_bytes(RS, V, k) if p is None else lib.spacap_sample_word_nucleus_workspace_bytes(RS, V)
+        ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
         ys = torch.empty(RS, n_words, dtype=torch.long, device=dev)
         score = torch.zeros(RS, dtype=torch.float32, device=dev)
         length = torch.zeros(RS, dtype=torch.int32, device=dev)
@@ -268,10 +281,16 @@ def sample_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, num_s
             elif t > 1:
                 x = s.xw
             n = s.position(x, t, attn)
-            if t >= 1:
+            if t >= 1 and p is None:
                 # word t - 1 of every row, its log-probability into the row's state, and xw = lut[word] sqrt(d) + pe[t]
                 check(lib.spacap_sample_word_f32(n.data_ptr(), s.gwp.data_ptr(), s.gb.data_ptr(), RS, V, k, 1.0 / tau, seed_host, seed_dev,
                                                  n_words, t - 1, int(eos), s.lut.data_ptr(), s.sqrt_d,
                                                  s.pe_rows[min(t, T - 1)].data_ptr(), ys.data_ptr(), score.data_ptr(), length.data_ptr(),
                                                  fin.data_ptr(), s.xw.data_ptr(), ws.data_ptr(), st), "spacap_sample_word_f32")
+            elif t >= 1:          # the same from the row's nucleus
+                check(lib.spacap_sample_word_nucleus_f32(n.data_ptr(), s.gwp.data_ptr(), s.gb.data_ptr(), RS, V, p, 1.0 / tau, seed_host,
+                                                         seed_dev, n_words, t - 1, int(eos), s.lut.data_ptr(), s.sqrt_d,
+                                                         s.pe_rows[min(t, T - 1)].data_ptr(), ys.data_ptr(), score.data_ptr(),
+                                                         length.data_ptr(), fin.data_ptr(), s.xw.data_ptr(), ws.data_ptr(), st),
+                      "spacap_sample_word_nucleus_f32")
     return ys.view(R, S, n_words), score.view(R, S), length.view(R, S)

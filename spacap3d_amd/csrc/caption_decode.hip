@@ -14,7 +14,10 @@
 //   vocab_gumbel_kernel + sample_next_kernel : word = arg-max of logit / tau + Gumbel noise (the greedy kernel's workgroup shape
 //       and logit tile; the noise is a hash of (row, step, word)), its log-probability from an online (max, sum exp), the row's
 //       score / length / finished flag and the next input row; with top_k the candidates are beam_topw_kernel's k best
-// No logits reach HBM; no step reads a value back on the host.
+//   vocab_logits_kernel + nucleus_next_kernel : nucleus (top-p) sampling -- the same draw restricted to the words whose strictly
+//       more probable words hold less than p of softmax(logit / tau); the set needs a whole row, so this mode alone writes
+//       the logits to HBM (one image in the workspace) and a workgroup per row reads them back
+// Otherwise no logits reach HBM; no step reads a value back on the host.
 //
 // The logit tile -- row split, weight staging, the same six piece products in the same order on the same two accumulators -- the
 // first-maximum compare and the slicing of the vocabulary over workgroups are defined ONCE below: that is what makes a beam of
@@ -692,6 +695,154 @@ __global__ __launch_bounds__(256) void sample_next_kernel(const float *__restric
   st4(xw + (size_t)r * VA_D + 4 * c4, f32x4{e[0] * scale + p[0], e[1] * scale + p[1], e[2] * scale + p[2], e[3] * scale + p[3]});
 }
 
+// ---- nucleus (top-p) sampling: the draw restricted to the words whose more probable words hold less than p ---------------------
+// DESIGN.md section 7i, "Top-p", restated by tests/nucleus_restated.py: q = softmax(l / tau), A_v = the mass of the words with
+// l_u > l_v, nucleus = { v : A_v < p }; the row draws the first maximum of z over the nucleus, z and its noise as above.  The
+// set needs the whole row at once, so this mode alone writes the logits to HBM: vocab_logits_kernel stores the image
+// f32 [rows][ld], ld = V rounded up to whole chunks, and nucleus_next_kernel reads each row back once.
+constexpr int NUC_MAX_V = 16384;      // a row's (key, q) pairs sit in LDS: 8 bytes a word, 128 KB
+inline int nuc_ld(int V) { return (V + VA_CHUNK - 1) / VA_CHUNK * VA_CHUNK; }
+
+// vocab_argmax_kernel's grid, row split, staging and logit tile (the macros above).  The 16 x 64 logits of a chunk go through
+// LDS so that a row's 64 words leave as 16 sixteen-byte stores of one 256-byte run: ld is a multiple of 64 floats, every run is
+// whole lines.  Words V .. ld - 1 of the last chunk are written too (the repeated last weight row, no bias) and never read.
+__global__ __launch_bounds__(256) void vocab_logits_kernel(const float *__restrict__ x, const __bf16 *__restrict__ Wp, const float *__restrict__ bias,
+                                                           long R, int V, int per_slice, int ld, float *__restrict__ img) {
+  __shared__ __attribute__((aligned(16))) __bf16 s_w[VA_STAGE_ELEMS];
+  __shared__ __attribute__((aligned(16))) float s_o[VA_ROWS][VA_CHUNK + 4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
+  const long row0 = (long)blockIdx.x * VA_ROWS;
+  const int sl = blockIdx.y;
+  const int v_beg = sl * per_slice, v_end = min(V, v_beg + per_slice);
+  SPACAP_VA_SPLIT_ROWS();   // bf16x8 a[kc][piece]
+  SPACAP_VA_STAGING();      // stg, fetch(v0)
+  fetch(v_beg < V ? v_beg : 0);
+  for (int v0 = v_beg; v0 < v_end; v0 += VA_CHUNK) {
+    __syncthreads();        // (also: every thread is done reading s_o of the chunk before)
+    SPACAP_VA_STORE_STAGE();
+    __syncthreads();
+    if (v0 + VA_CHUNK < v_end) fetch(v0 + VA_CHUNK);
+    const int v = v0 + 16 * w + l15;                    // this lane's word of the chunk
+    SPACAP_VA_TILE();                                   // acc, acc2
+    const float bsv = v < V ? bias[v] : 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s_o[4 * lg + u][16 * w + l15] = (acc[u] + acc2[u]) + bsv;   // (the greedy kernel's logit, bit for bit)
+    __syncthreads();
+    const int row = tid >> 4, c = 4 * (tid & 15);
+    if (row0 + row < R) st4(img + (size_t)(row0 + row) * ld + v0 + c, ld4(&s_o[row][c]));
+  }
+}
+
+// a > b <=> key(a) > key(b) for floats that are not NaN; -0 counts as +0, as in the float compare
+__device__ __forceinline__ unsigned nucleus_key(float l) {
+  const unsigned u = __float_as_uint(l + 0.f);
+  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float nucleus_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
+
+// The sum of the four waves' values in one fixed order.  s_red: 4 floats nobody else writes before the next barrier.
+__device__ __forceinline__ float nucleus_block_sum(float v, float *s_red, int tid) {
+  v = wave_sum(v);          // a butterfly: every lane holds the same bits
+  if ((tid & 63) == 0) s_red[tid >> 6] = v;
+  __syncthreads();
+  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+// One workgroup per row; thread t owns words t, t + 256, ...  The row's logits are read once, into LDS as their keys (s_kq, V
+// pairs of dynamic LDS; a thread reads back its own words only).  M = max l; T = sum exp((l - M) / tau) and S = sum exp(l - M),
+// each in one fixed order (per thread by increasing word, a butterfly over the wave, then the four waves); the terms
+// q = exp((l - M) / tau) are kept beside the keys.  The threshold key: the smallest 32-bit key k with
+// mass(k) = sum_{key(l_u) > k} q_u < p T, found bit by bit from the top -- bit b stays 0 when mass(k | (2^b - 1)) < p T: 32
+// passes over the pairs (with exp recomputed in every pass a word choice took 165 instead of 141 us at 2 048 x 3 001).  mass()
+// adds the SAME floats in the same fixed order with 0 for the words outside the set, so it is monotone in k in float arithmetic
+// and the bisection is valid.  The nucleus is { v : key(l_v) >= k }: words with equal logits share a key and enter together,
+// and the largest logit is always in (mass = 0 < p T).  Then the first maximum of z over the nucleus and the row's state as
+// sample_next_kernel.  No atomics; the same inputs give the same bits.
+__global__ __launch_bounds__(256) void nucleus_next_kernel(const float *__restrict__ img, int ld, float top_p, float inv_tau, unsigned long long seed,
+                                                           const unsigned long long *__restrict__ seed_dev, int V, int n_words, int step,
+                                                           int eos, const float *__restrict__ lut, float scale, const float *__restrict__ pe_row,
+                                                           long long *__restrict__ ys, float *score, int *length, int *fin,
+                                                           float *__restrict__ xw) {
+  extern __shared__ __attribute__((aligned(16))) uint2 s_kq[];   // (key of l, bits of q)
+  __shared__ float s_red[2][4];
+  __shared__ float s_z[4], s_wl[4];
+  __shared__ int s_wi[4];
+  const int tid = threadIdx.x;
+  const size_t r = blockIdx.x;
+  const float *row = img + r * (size_t)ld;
+  float M = -INFINITY;
+  for (int v = tid; v < V; v += 256) {
+    const float l = row[v];
+    s_kq[v].x = nucleus_key(l);
+    M = fmaxf(M, l);
+  }
+  M = wave_max(M);
+  if ((tid & 63) == 0) s_red[1][tid >> 6] = M;
+  __syncthreads();
+  M = fmaxf(fmaxf(s_red[1][0], s_red[1][1]), fmaxf(s_red[1][2], s_red[1][3]));
+  float t = 0.f, s = 0.f;
+  for (int v = tid; v < V; v += 256) {
+    const float d = nucleus_unkey(s_kq[v].x) - M, q = expf(d * inv_tau);
+    s_kq[v].y = __float_as_uint(q);
+    t += q, s += expf(d);
+  }
+  // The two scratch rows alternate from here on: a row is written again only behind the barrier of the sum that followed its
+  // last read (the maxima of row 1 were read before the barrier inside T's sum).
+  const float T = nucleus_block_sum(t, s_red[0], tid);
+  const float S = nucleus_block_sum(s, s_red[1], tid);
+  const float bar = top_p * T;
+  unsigned k = 0u;
+  for (int b = 31; b >= 0; --b) {
+    const unsigned cand = k | ((1u << b) - 1u);
+    float m = 0.f;
+    for (int v = tid; v < V; v += 256) {
+      const uint2 e = s_kq[v];
+      m += e.x > cand ? __uint_as_float(e.y) : 0.f;
+    }
+    if (!(nucleus_block_sum(m, s_red[(b & 1) ^ 1], tid) < bar)) k |= 1u << b;   // (b = 31 takes row 0: S sits in row 1)
+  }
+  const DropSeed sd = make_seed(seed, seed_dev);
+  const unsigned long long nbase = ((unsigned long long)r * (unsigned long long)n_words + (unsigned long long)step) * (unsigned long long)V;
+  float bz = -INFINITY, bl = -INFINITY;
+  int bi = NO_WORD;
+  for (int v = tid; v < V; v += 256) {
+    const unsigned key = s_kq[v].x;
+    if (key >= k) {
+      const float l = nucleus_unkey(key);
+      const float z = l * inv_tau + gumbel_noise(nbase + (unsigned long long)v, sd);
+      if (z > bz) bz = z, bi = v, bl = l;       // (the thread's words arrive in increasing order)
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float oz = __shfl_xor(bz, o), ol = __shfl_xor(bl, o);
+    const int oi = __shfl_xor(bi, o);
+    if (SPACAP_FIRST_MAX(oz, oi, bz, bi)) bz = oz, bi = oi, bl = ol;
+  }
+  if ((tid & 63) == 0) s_z[tid >> 6] = bz, s_wi[tid >> 6] = bi, s_wl[tid >> 6] = bl;
+  __syncthreads();
+  if (tid >= 32) return;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float oz = s_z[q], ol = s_wl[q];
+    const int oi = s_wi[q];
+    if (q == 0 || SPACAP_FIRST_MAX(oz, oi, bz, bi)) bz = oz, bi = oi, bl = ol;
+  }
+  const float logp = (bl - M) - logf(S);
+  const int f = fin[r];
+  const int word = f ? eos : min(max(bi, 0), V - 1);
+  if (tid == 0) {
+    ys[r * (size_t)n_words + step] = word;
+    if (!f) {
+      score[r] += logp;
+      length[r] = step + 1;
+      if (word == eos) fin[r] = 1;
+    }
+  }
+  const f32x4 e = ld4(lut + (size_t)word * VA_D + 4 * tid), p = ld4(pe_row + 4 * tid);
+  st4(xw + r * VA_D + 4 * tid, f32x4{e[0] * scale + p[0], e[1] * scale + p[1], e[2] * scale + p[2], e[3] * scale + p[3]});
+}
+
 }  // namespace
 
 extern "C" int spacap_decode_attn_f32(const float *qkv, float *kcache, float *vcache, long R, int h, int d_k, int T, int t, float scale,
@@ -868,6 +1019,44 @@ extern "C" int spacap_sample_word_f32(const float *x, const void *Wp, const floa
   hipLaunchKernelGGL(sample_next_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, s, pz, pw, pl, pms, ns, top_lp, top_wd, top_k, inv_tau,
                      (unsigned long long)seed, sdev, rows, V, n_words, step, eos, lut, scale, pe_row, reinterpret_cast<long long *>(ys), score,
                      reinterpret_cast<int *>(length), reinterpret_cast<int *>(finished), xw);
+  SPACAP_CHECK_LAUNCH(what);
+  return SPACAP_OK;
+}
+
+/* Nucleus (top-p) sampling ("Top-p"): spacap_sample_word_f32's step with the draw restricted to the
+   words v whose strictly more probable words hold less than top_p of softmax(logits * inv_tau).  Two launches:
+   vocab_logits_kernel writes the logits to the workspace -- f32 [rows][V rounded up to a multiple of 64], the whole
+   workspace -- and nucleus_next_kernel, one workgroup per row, finds the threshold, draws and updates the row.  V <= 16 384:
+   the row kernel keeps 8 bytes a word in LDS. */
+extern "C" size_t spacap_sample_word_nucleus_workspace_bytes(long rows, int V) {
+  return rows > 0 && V >= 1 && V <= NUC_MAX_V ? (size_t)rows * nuc_ld(V) * sizeof(float) : 0;
+}
+
+extern "C" int spacap_sample_word_nucleus_f32(const float *x, const void *Wp, const float *bias, long rows, int V, float top_p, float inv_tau,
+                                              uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos, const float *lut,
+                                              float scale, const float *pe_row, int64_t *ys, float *score, int32_t *length,
+                                              int32_t *finished, float *xw, void *workspace, spacap_stream_t stream) {
+  const char *what = "spacap_sample_word_nucleus_f32";
+  SPACAP_REQUIRE(rows >= 0 && V >= 1 && V <= NUC_MAX_V, "%s: (rows=%ld, V=%d) unsupported: rows >= 0 and 1 <= V <= %d", what, rows, V,
+                 NUC_MAX_V);
+  SPACAP_REQUIRE(isfinite(top_p) && top_p > 0.f && top_p <= 1.f, "%s: top_p = %g must lie in (0, 1]", what, (double)top_p);
+  SPACAP_REQUIRE(isfinite(inv_tau) && inv_tau > 0.f, "%s: 1/temperature = %g must be finite and positive", what, (double)inv_tau);
+  SPACAP_REQUIRE(n_words >= 1 && step >= 0 && step < n_words, "%s: (n_words=%d, step=%d) unsupported: 0 <= step < n_words", what, n_words, step);
+  SPACAP_REQUIRE(eos >= 0 && eos < V, "%s: eos=%d outside the vocabulary (V=%d)", what, eos, V);
+  if (rows == 0) return SPACAP_OK;
+  SPACAP_REQUIRE(x && Wp && bias && lut && pe_row && ys && score && length && finished && xw && workspace, "%s: null pointer", what);
+  SPACAP_REQUIRE(aligned16(x, Wp, lut, pe_row, xw, workspace), "%s: x, Wp, lut, pe_row, xw and workspace must be 16-byte aligned", what);
+  SPACAP_REQUIRE(rows <= 2147483647L, "%s: too many rows", what);
+  hipStream_t s = spacap::as_stream(stream);
+  const int ns = va_slices(rows, V), per = va_per_slice(V, ns), ld = nuc_ld(V);
+  float *img = static_cast<float *>(workspace);
+  static unsigned long long lds_ok = 0;
+  SPACAP_CHECK_HIP(spacap::allow_dynamic_lds(reinterpret_cast<const void *>(&nucleus_next_kernel), NUC_MAX_V * 8, lds_ok), what);
+  hipLaunchKernelGGL(vocab_logits_kernel, dim3((unsigned)((rows + VA_ROWS - 1) / VA_ROWS), ns), dim3(256), 0, s, x,
+                     static_cast<const __bf16 *>(Wp), bias, rows, V, per, ld, img);
+  hipLaunchKernelGGL(nucleus_next_kernel, dim3((unsigned)rows), dim3(256), (size_t)V * 8, s, img, ld, top_p, inv_tau,
+                     (unsigned long long)seed, reinterpret_cast<const unsigned long long *>(seed_dev), V, n_words, step, eos, lut, scale,
+                     pe_row, reinterpret_cast<long long *>(ys), score, reinterpret_cast<int *>(length), reinterpret_cast<int *>(finished), xw);
   SPACAP_CHECK_LAUNCH(what);
   return SPACAP_OK;
 }

@@ -844,8 +844,9 @@ class Evaluator:
     greedy decoding, the forward then also returns ``lang_cap_score``).  ``lang_cap`` keeps its shape and
     meaning, so ``caption_eval``, ``predictions`` and ``detection_ap`` consume it unchanged.
 
-    ``sample``: ``dict(num_samples=S, temperature=tau, top_k=k, seed=None)`` (every key optional; exclusive with ``beam_size`` >
-    1): sampled decoding instead (DESIGN.md section 7i) -- sets the captioner's ``num_samples`` / ``temperature`` / ``top_k``;
+    ``sample``: ``dict(num_samples=S, temperature=tau, top_k=k, top_p=p, seed=None)`` (every key optional; exclusive with ``beam_size`` >
+    1): sampled decoding instead -- sets the captioner's ``num_samples`` / ``temperature`` / ``top_k`` / ``top_p``
+    (``top_p`` in (0, 1): nucleus sampling; not together with ``top_k`` >= 1);
     ``lang_cap`` is sample 0 and the forward also returns ``lang_cap_score``, ``lang_cap_samples``, ``lang_cap_sample_scores``
     and ``lang_cap_sample_lengths``.  ``seed``: an integer repeats the same draws at every call; None draws new ones."""
 
@@ -866,15 +867,16 @@ class Evaluator:
         if sample is not None:
             if cap is None or not hasattr(cap, "num_samples"):
                 raise ValueError("Evaluator: sample needs a model with a Transformer captioner")
-            unknown = set(sample) - {"num_samples", "temperature", "top_k", "seed"}
+            unknown = set(sample) - {"num_samples", "temperature", "top_k", "top_p", "seed"}
             if unknown:
                 raise ValueError(f"Evaluator: sample has unknown keys {sorted(unknown)}")
             if int(cap.beam_size) > 1:
                 raise ValueError("Evaluator: sample and beam_size > 1 exclude each other")
             S, tau, k = int(sample.get("num_samples", 1)), float(sample.get("temperature", 1.0)), int(sample.get("top_k", 0))
             from .sampling import check_arguments
-            check_arguments("Evaluator: sample", S, tau, k, cap.model.generator.proj.out_features)
-            cap.num_samples, cap.temperature, cap.top_k = S, tau, k
+            top_p = None if sample.get("top_p") is None else float(sample["top_p"])
+            check_arguments("Evaluator: sample", S, tau, k, cap.model.generator.proj.out_features, top_p)
+            cap.num_samples, cap.temperature, cap.top_k, cap.top_p = S, tau, k, top_p
             cap.sample_seed = None if sample.get("seed") is None else int(sample["seed"])
         self.post_kw = None
         for name, given in (("predictions", predictions), ("detection_ap", detection_ap), ("caption_eval", caption_eval)):

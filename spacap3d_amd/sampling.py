@@ -9,6 +9,13 @@ dropout keep mask's hash (csrc/dropout.hpp) of the flat index ``(rho n_words + i
 descending, the smaller word first) and z is formed from their log-probabilities -- the logits minus one constant per row --
 with the noise of their word id.  ``logp = logit_word - logsumexp(logit)`` whatever tau and k are; ``score`` sums it through the
 row's first eos, ``length`` is the position of that eos plus one (``n_words``: none), and behind it the row emits eos.
+
+Nucleus sampling, ``top_p`` = p in (0, 1) (``tests/nucleus_restated.py``): with ``q = softmax(logit / tau)`` -- the tempered
+distribution -- and ``A_v`` the sum of ``q_u`` over the words with ``logit_u > logit_v``, the mass strictly more probable than v,
+the nucleus is ``{v : A_v < p}``.  Words with equal logits enter or stay out together, the most probable word is always in, and
+no sort order or tie rule takes part.  The row draws the first maximum of the same ``z_v`` over the nucleus, so a row whose
+unrestricted draw lies in its nucleus draws that word; ``logp`` stays the untempered, untruncated one.  ``None`` or 1.0 is the
+unrestricted path.  One restriction at a time: ``top_p`` < 1 together with ``top_k`` >= 1 is refused.
 """
 import math
 
@@ -18,15 +25,38 @@ _M32 = 0xFFFFFFFF
 _GOLDEN = 0x9E3779B97F4A7C15 - (1 << 64)      # the seed's 64-bit golden-ratio constant as a two's-complement int64
 
 
-def check_arguments(who, num_samples, temperature, top_k, V=None):
+def check_arguments(who, num_samples, temperature, top_k, V=None, top_p=None):
     """The argument rules of every entry to sampled decoding, in one place: S >= 1, tau finite and positive, ``top_k`` in
-    0..8 and at most the vocabulary size V (where known).  Raises ValueError naming ``who``."""
+    0..8 and at most the vocabulary size V (where known), ``top_p`` None or in (0, 1] and below 1 only with ``top_k`` = 0.
+    Raises ValueError naming ``who``."""
     if num_samples < 1:
         raise ValueError(f"{who}: num_samples {num_samples} < 1")
     if not (math.isfinite(temperature) and temperature > 0.0):
         raise ValueError(f"{who}: temperature {temperature} must be finite and positive")
     if not 0 <= top_k <= 8 or (V is not None and top_k > V):
         raise ValueError(f"{who}: top_k {top_k} unsupported (0 <= top_k <= 8 and top_k <= vocabulary size{'' if V is None else ' ' + str(V)})")
+    if top_p is not None:
+        if not 0.0 < top_p <= 1.0:                                 # (NaN fails both compares)
+            raise ValueError(f"{who}: top_p {top_p} must lie in (0, 1]")
+        if top_p < 1.0 and top_k >= 1:
+            raise ValueError(f"{who}: top_p {top_p} and top_k {top_k}: one restriction at a time")
+
+
+def nucleus_of(top_p):
+    """The p of a nucleus restriction, or None where ``top_p`` (None or 1.0) asks for the unrestricted path"""
+    return None if top_p is None or float(top_p) == 1.0 else float(top_p)
+
+
+def nucleus_mask(logits, tau, p):
+    """(N, V) bool: word v of a row is in when the words with a larger logit hold less than p of softmax(logits / tau).  The
+    mass is summed in float64 along the logits in descending order; a run of equal logits takes the mass in front of the run."""
+    srt, order = torch.sort(logits.double(), dim=1, descending=True)
+    q = torch.softmax(srt * (1.0 / tau), dim=1)
+    above = torch.cumsum(q, 1) - q
+    starts = torch.ones_like(srt, dtype=torch.bool)
+    starts[:, 1:] = srt[:, 1:] != srt[:, :-1]
+    above = torch.cummax(torch.where(starts, above, torch.zeros_like(above)), 1).values      # (`above` never decreases along a row)
+    return torch.zeros_like(starts).scatter_(1, order, above < p)
 
 
 def seed_words(seed, seed_dev=None, device=None):
@@ -68,11 +98,12 @@ def _first_max(z, words):
 
 
 @torch.no_grad()
-def sample(step_fn, R, S, n_words, sos, eos, temperature=1.0, top_k=0, seed=0, seed_dev=None, device=None):
+def sample(step_fn, R, S, n_words, sos, eos, temperature=1.0, top_k=0, seed=0, seed_dev=None, device=None, top_p=None):
     """``step_fn(i, words)`` returns the (R S, V) logits (before log-softmax) of word i of every row; ``words`` (R S,) int64
     are the newest words (``sos`` at i = 0).  Returns a dict: ``ys`` (R, S, n_words) int64, ``score`` (R, S) float32,
     ``length`` (R, S) int32 and ``gap`` (n_words, R S) float32: per row and step the best z minus the second-best one among
-    the candidates (inf with one candidate; recorded for finished rows too)."""
+    the candidates (inf with one candidate; recorded for finished rows too).  ``top_p``: the nucleus restriction of the module's
+    docstring (None or 1.0: none)."""
     from .beam_search import select_top
     R, S, n_words, sos, eos, k, tau = int(R), int(S), int(n_words), int(sos), int(eos), int(top_k), float(temperature)
     N = R * S
@@ -83,7 +114,7 @@ def sample(step_fn, R, S, n_words, sos, eos, temperature=1.0, top_k=0, seed=0, s
         logits = step_fn(i, words).float()
         dev, V = logits.device, logits.shape[1]
         if score is None:
-            check_arguments("sample", S, tau, k, V)
+            check_arguments("sample", S, tau, k, V, top_p)
             score = torch.zeros(N, dtype=torch.float32, device=dev)
             fin = torch.zeros(N, dtype=torch.bool, device=dev)
             length = torch.zeros(N, dtype=torch.int32, device=dev)
@@ -94,6 +125,8 @@ def sample(step_fn, R, S, n_words, sos, eos, temperature=1.0, top_k=0, seed=0, s
         if k == 0:
             cand = torch.arange(V, dtype=torch.int64, device=dev).unsqueeze(0).expand(N, V)
             z = logits * (1.0 / tau) + gumbel_noise(base + cand, lo, hi)
+            if nucleus_of(top_p) is not None:
+                z = torch.where(nucleus_mask(logits, tau, nucleus_of(top_p)), z, torch.full_like(z, float("-inf")))
         else:
             vals, cand = select_top(logp, k)
             z = vals * (1.0 / tau) + gumbel_noise(base + cand, lo, hi)

@@ -54,11 +54,12 @@ def reward_weights(reward):
 
 
 class SelfCritical:
-    """``SelfCritical(corpus, sos, eos, num_samples=5, temperature=1.0, top_k=0, baseline="greedy", seed=None)``.
+    """``SelfCritical(corpus, sos, eos, num_samples=5, temperature=1.0, top_k=0, baseline="greedy", seed=None, top_p=None)``.
 
     ``corpus``: a ``CaptionCorpus`` (its key table maps ``(dataset_idx, object_id)`` to the references of the referred object).
     ``num_samples`` = S captions are drawn per scene from softmax(logits / ``temperature``), over the whole vocabulary or the
-    ``top_k`` <= 8 most probable words (``sampling.check_arguments``).  ``baseline``: ``"greedy"`` -- the reward of the greedy
+    ``top_k`` <= 8 most probable words, or -- ``top_p`` in (0, 1), with ``top_k`` = 0 -- the row's nucleus
+    (``sampling.check_arguments``; ``sampling.py`` states the set).  ``baseline``: ``"greedy"`` -- the reward of the greedy
     caption of the same proposal -- or ``"samples"`` -- per sample the mean reward of the scene's other samples (S >= 2; no
     greedy decode runs).  ``seed``: an integer draws the same captions at every call, None new ones per call.
 
@@ -77,7 +78,7 @@ class SelfCritical:
     ``lang_label`` and ``lang_ids``.  Anything else raises ``ValueError``."""
 
     def __init__(self, corpus, sos, eos, num_samples=5, temperature=1.0, top_k=0, baseline="greedy", seed=None,
-                 proposals="referred", max_proposals=16, near_threshold=0.3, reward="cider", xe_weight=0.0):
+                 proposals="referred", max_proposals=16, near_threshold=0.3, reward="cider", xe_weight=0.0, top_p=None):
         if not isinstance(corpus, CaptionCorpus):
             raise TypeError("self_critical: corpus must be a CaptionCorpus")
         if not (0 <= int(sos) < MAX_IDS and 0 <= int(eos) < MAX_IDS):
@@ -85,7 +86,8 @@ class SelfCritical:
         self.corpus = corpus
         self.sos, self.eos = int(sos), int(eos)
         self.num_samples, self.temperature, self.top_k = int(num_samples), float(temperature), int(top_k)
-        check_arguments("self_critical", self.num_samples, self.temperature, self.top_k)
+        self.top_p = None if top_p is None else float(top_p)
+        check_arguments("self_critical", self.num_samples, self.temperature, self.top_k, top_p=self.top_p)
         if baseline not in BASELINES:
             raise ValueError(f"self_critical: baseline {baseline!r} unknown (one of {BASELINES})")
         if baseline == "samples" and self.num_samples < 2:

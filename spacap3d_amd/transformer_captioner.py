@@ -540,8 +540,7 @@ class TransformerDecoderModel(nn.Module):
             indicator = (src.gather(1, sel) + memory.gather(1, sel)).squeeze(1)
             if not cd.decode_supported(dec.layers, indicator, n_words):
                 raise RuntimeError("self_critical: this decoder stack is not supported by the fused decode")
-            ys, score, _ = cd.sample_decode(dec, gen, te[0], te[1].pe, indicator, sc.sos, sc.eos, n_words, S, sc.temperature,
-                                            sc.top_k, sc.seed)
+            ys, score, _ = self._scst_draw(cd, sc, dec, gen, te, indicator, n_words)
             didx, oid = ep["dataset_idx"].reshape(-1), ep["object_id"].reshape(-1)
             words = ys.view(B * S, n_words)
             # (with the settings of section 7l the reward and the baseline's reward come from the mixed launch, with their terms)
@@ -621,6 +620,16 @@ class TransformerDecoderModel(nn.Module):
         words = pad(words, (0, W - words.shape[1])) if words.shape[1] < W else words
         return gt, tok, words, Tg - 2
 
+    @staticmethod
+    def _scst_draw(cd, sc, dec, gen, te, indicator, n_words):
+        """The S samples of every row of ``indicator`` for a self-critical step: ``caption_decode.sample_decode`` with the
+        sampler's settings."""
+        got = cd.sample_decode(dec, gen, te[0], te[1].pe, indicator, sc.sos, sc.eos, n_words, sc.num_samples, sc.temperature, sc.top_k,
+                               sc.seed, sc.top_p)
+        if got is None:
+            raise ValueError(f"self_critical: top_p needs a vocabulary of at most {cd.NUCLEUS_MAX_V} words")
+        return got
+
     def _self_critical_matched(self, ep, sc, prep, src, memory):
         """The same step over every matched object of a scene: ``sc.select`` pairs up to M annotated
         objects per scene with their nearest proposals, the B M groups play the part the B scenes play above -- S samples, a
@@ -654,8 +663,7 @@ class TransformerDecoderModel(nn.Module):
             indicator = (src.gather(1, sel) + memory.gather(1, sel)).masked_fill(~count.unsqueeze(-1), 0.0).reshape(B * M, D)
             if not cd.decode_supported(dec.layers, indicator, n_words):
                 raise RuntimeError("self_critical: this decoder stack is not supported by the fused decode")
-            ys, score, _ = cd.sample_decode(dec, gen, te[0], te[1].pe, indicator, sc.sos, sc.eos, n_words, S, sc.temperature,
-                                            sc.top_k, sc.seed)
+            ys, score, _ = self._scst_draw(cd, sc, dec, gen, te, indicator, n_words)
             didx, oid = ep["dataset_idx"].reshape(B, 1).expand(B, M).reshape(-1), obj.reshape(-1)
             words = ys.view(B * M * S, n_words)
             reward, _, length, tf_tok, *terms = sc.rewards(words, didx, oid, S, terms=sc.mixed)
@@ -759,17 +767,19 @@ class TransformerDecoderModel(nn.Module):
     beam_generic = False
     last_beam_trace = None
     # Sampled decoding, set the same way: num_samples = S >= 1 draws S captions per proposal from
-    # softmax(logits / temperature), over the whole vocabulary (top_k = 0) or the top_k <= 8 most probable words; 0 = off.
+    # softmax(logits / temperature), over the whole vocabulary (top_k = 0), the top_k <= 8 most probable words or -- top_p in
+    # (0, 1), with top_k = 0 -- the row's nucleus; num_samples = 0 = off.
     # sample_generic sends it through sampling.sample (parity tests); last_sample_trace then holds its per-step gaps.
     num_samples = 0
     temperature = 1.0
     top_k = 0
+    top_p = None
     sample_generic = False
     sample_seed = None          # an integer: the same draws at every call (forward_eval's sample_seed, when that is None)
     last_sample_trace = None
 
     def forward_eval(self, ep, use_cache=True, beam_size=None, length_penalty=None, num_samples=None, temperature=None, top_k=None,
-                     sample_seed=None):
+                     sample_seed=None, top_p=None):
         """Greedy decoding of B*K captions (:402-453).  The reference re-runs the 6-layer encoder AND the whole
         decoder prefix at each of the 31 steps; the encoder output does not depend on the words (computed once),
         and with ``use_cache`` the decoder keeps the keys / values of earlier positions so that each step only
@@ -784,7 +794,9 @@ class TransformerDecoderModel(nn.Module):
 
         ``num_samples`` = S >= 1 (default: the module attribute, 0 = off): sampled decoding instead (the reference has none;
         DESIGN.md section 7i) -- S captions per proposal drawn from softmax(logits / ``temperature``), over the whole vocabulary
-        (``top_k`` = 0) or the ``top_k`` <= 8 most probable words.  ``lang_cap`` (B, K, n_words) is sample 0 (eos repeats after
+        (``top_k`` = 0), the ``top_k`` <= 8 most probable words, or -- ``top_p`` in (0, 1), not together with ``top_k`` >= 1 --
+        the row's nucleus: the words whose strictly more probable words hold less than ``top_p`` of that distribution
+        (``sampling.py``).  ``lang_cap`` (B, K, n_words) is sample 0 (eos repeats after
         the first eos) and ``lang_cap_score`` (B, K) its summed log-probability under the model's own distribution;
         ``lang_cap_samples`` (B, K, S, n_words), ``lang_cap_sample_scores`` and ``lang_cap_sample_lengths`` (B, K, S) hold every
         sample.  ``sample_seed``: an integer draws the same captions at every call; None draws new ones per call and, in a
@@ -800,13 +812,14 @@ class TransformerDecoderModel(nn.Module):
         tau = float(self.temperature if temperature is None else temperature)
         topk = int(self.top_k if top_k is None else top_k)
         sample_seed = self.sample_seed if sample_seed is None else sample_seed
+        top_p = self.top_p if top_p is None else top_p
         if S < 0 or (S < 1 and num_samples is not None):      # (the attribute's 0 means off; an argument asks for samples)
             raise ValueError(f"forward_eval: num_samples {S} < 1")
         if S >= 1:
             from .sampling import check_arguments
             if W > 1:
                 raise ValueError("forward_eval: sampling and beam search (beam_size > 1) exclude each other")
-            check_arguments("forward_eval", S, tau, topk, self.model.generator.proj.out_features)
+            check_arguments("forward_eval", S, tau, topk, self.model.generator.proj.out_features, top_p)
             if not use_cache:
                 raise ValueError("forward_eval: sampling keeps key / value caches (use_cache=False is the greedy parity path)")
         obj_features = ep["aggregated_vote_features"]
@@ -851,11 +864,12 @@ class TransformerDecoderModel(nn.Module):
             sos, eos = self.word_to_idx["sos"], self.word_to_idx["eos"]
             if fused and not self.sample_generic:
                 # the greedy loop below at B K S rows with a drawn word in place of the arg-max (caption_decode.sample_decode)
-                self.last_sample_trace = None
                 got = cd.sample_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), sos, eos, MAX_DES_LEN + 1,
-                                       S, tau, topk, sample_seed)
-                return self._sample_outputs(ep, B, K, *got)
-            return self._sample_generic(ep, B, K, S, tau, topk, sample_seed, dec, indicator)
+                                       S, tau, topk, sample_seed, top_p)
+                if got is not None:       # (None: a nucleus over more words than the fused entry takes)
+                    self.last_sample_trace = None
+                    return self._sample_outputs(ep, B, K, *got)
+            return self._sample_generic(ep, B, K, S, tau, topk, sample_seed, dec, indicator, top_p)
         if beam and fused and not self.beam_generic:
             # the greedy loop below at B K W rows: top-W log-probabilities, one selection per sequence, attention through an
             # ancestor table (caption_decode.beam_decode, csrc/caption_decode.hip)
@@ -914,7 +928,7 @@ class TransformerDecoderModel(nn.Module):
         ep["lang_cap_sample_lengths"] = length.view(B, K, -1)
         return ep
 
-    def _sample_generic(self, ep, B, K, S, tau, topk, seed, dec, indicator):
+    def _sample_generic(self, ep, B, K, S, tau, topk, seed, dec, indicator, top_p=None):
         """Sampled decoding through the cached per-operator decoder (``decode_incremental``): everything the fused path does not
         take -- late guide, other head counts, the CPU oracle backend.  Row r S + s is sample s of sequence r."""
         from .sampling import sample
@@ -931,7 +945,7 @@ class TransformerDecoderModel(nn.Module):
             return self.model.generator.proj(self._cached_step(dec, caches, ind, i, words))
 
         got = sample(step_fn, R, S, MAX_DES_LEN + 1, self.word_to_idx["sos"], self.word_to_idx["eos"], tau, topk, seed, seed_dev,
-                     device=indicator.device)
+                     device=indicator.device, top_p=top_p)
         self.last_sample_trace = {"gap": got["gap"]}     # (n_words, R S): for parity tests
         return self._sample_outputs(ep, B, K, got["ys"], got["score"], got["length"])
 
