@@ -997,6 +997,36 @@ int spacap_sample_word_nucleus_f32(const float *x, const void *Wp, const float *
                                    uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos, const float *lut, float scale,
                                    const float *pe_row, int64_t *ys, float *score, int32_t *length, int32_t *finished, float *xw,
                                    void *workspace, spacap_stream_t stream);
+
+/* ---- caption decoding over the kept proposals only (csrc/decode_select.hip, restated by
+ * tests/decode_select_restated.py).  The decoders above take any number of independent rows; these entry points pack the
+ * flagged (scene, proposal) pairs into a dense row list, read the indicator rows through it and put the results back.  Every
+ * element of every output is written on every call; no atomics, no allocation, no host read; graph-capturable; the same
+ * inputs give the same bits. */
+
+/* The ordered compaction of n flags (mask u8 [n], any non-zero byte is set), in flat order, by one workgroup:
+ *   rows  i32 [capacity]   rows[i] = the flat index of the i-th set flag, -1 behind the last one;
+ *   slot  i32 [n]          slot[j] = the position of j in rows; -1 when flag j is clear or did not fit (overflow);
+ *   count i32 [2]          count[0] = the number of set flags, count[1] = min(count[0], capacity).
+ * 1 <= n <= 65 536, 1 <= capacity <= n; n == 0 returns SPACAP_OK and writes nothing. */
+int spacap_decode_select_i32(const uint8_t *mask, long n, long capacity, int32_t *rows, int32_t *slot, int32_t *count,
+                             spacap_stream_t stream);
+/* out f32 [capacity,d]: out[i] = obj[rows[i]] + memory[rows[i]] (memory null: obj[rows[i]] alone); a padding row (rows[i] < 0)
+ * is +0.0.  obj, memory f32 [n,d] with every rows[i] < n; d a multiple of 4; obj, memory and out 16-byte aligned (16-byte
+ * loads and stores).  0 <= capacity <= 65 536 (0: SPACAP_OK, nothing written). */
+int spacap_decode_gather_f32(const float *obj, const float *memory, const int32_t *rows, long capacity, int d, float *out,
+                             spacap_stream_t stream);
+/* out i64 [n,inner]: row j = ys[slot[j]] (ys i64 [capacity,inner], every slot[j] < capacity) where slot[j] >= 0; elsewhere the
+ * empty caption repeated: eos at every position l % L == 0, 0 elsewhere.  inner a multiple of L >= 1 (greedy: inner = L; all
+ * beams: W L; all samples: S L).  0 <= n <= 65 536 (0: SPACAP_OK, nothing written), 1 <= inner <= 2^20. */
+int spacap_decode_scatter_i64(const int64_t *ys, const int32_t *slot, long n, int inner, int L, int64_t eos, int64_t *out,
+                              spacap_stream_t stream);
+/* The same for scores (f32) and lengths (i32): out [n,inner], row j = vals[slot[j]] or `fill` at every element. */
+int spacap_decode_scatter_f32(const float *vals, const int32_t *slot, long n, int inner, float fill, float *out,
+                              spacap_stream_t stream);
+int spacap_decode_scatter_i32(const int32_t *vals, const int32_t *slot, long n, int inner, int32_t fill, int32_t *out,
+                              spacap_stream_t stream);
+
 /* Split-K product for the skinny feed-forward products (K = d_ff, N = 128: w_2 forward, the data gradient through w_1):
  * out[s][r][n] = sum_{k in slice s} a[r][k] Wop[k][n], Wop[k][n] = trans_w ? W[n][k] (W [N,K]) : W[k][n] (W [K,N]);
  * a [R,K], K and N multiples of 128, nsplit a divisor of K / 128 (spacap_tf_gemm_splits suggests the one that fills the

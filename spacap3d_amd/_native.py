@@ -111,6 +111,11 @@ SIGNATURES = {
     "spacap_scst_loss_bwd_f32": (_i, [_p] * 7 + [_i] * 3 + [_p, _p]),
     "spacap_scst_select_f32": (_i, [_p] * 6 + [_i] * 7 + [_f] + [_p] * 6 + [_p]),
     "spacap_dense_caption_select": (_i, [_p] * 5 + [_i] * 5 + [_p] * 7 + [_p]),
+    "spacap_decode_select_i32": (_i, [_p, _l, _l, _p, _p, _p] + [_p]),
+    "spacap_decode_gather_f32": (_i, [_p, _p, _p, _l, _i, _p] + [_p]),
+    "spacap_decode_scatter_i64": (_i, [_p, _p, _l, _i, _i, ctypes.c_int64, _p] + [_p]),
+    "spacap_decode_scatter_f32": (_i, [_p, _p, _l, _i, _f, _p] + [_p]),
+    "spacap_decode_scatter_i32": (_i, [_p, _p, _l, _i, _i, _p] + [_p]),
     "spacap_multiview_workspace_bytes": (ctypes.c_size_t, [_i]),
     "spacap_multiview_map_f32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, ctypes.c_size_t, _p, _p]),
     "spacap_multiview_features_f32": (_i, [_p, _i, _p, _p, _i, _i, _i] + [_f] * 7 + [_p, _p, _i, _i, _p, ctypes.c_size_t, _p, _p]),

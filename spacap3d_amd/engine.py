@@ -848,11 +848,28 @@ class Evaluator:
     1): sampled decoding instead -- sets the captioner's ``num_samples`` / ``temperature`` / ``top_k`` / ``top_p``
     (``top_p`` in (0, 1): nucleus sampling; not together with ``top_k`` >= 1);
     ``lang_cap`` is sample 0 and the forward also returns ``lang_cap_score``, ``lang_cap_samples``, ``lang_cap_sample_scores``
-    and ``lang_cap_sample_lengths``.  ``seed``: an integer repeats the same draws at every call; None draws new ones."""
+    and ``lang_cap_sample_lengths``.  ``seed``: an integer repeats the same draws at every call; None draws new ones.
+
+    ``decode``: ``"all"`` (default) decodes a caption for every proposal; ``"kept"`` (needs ``postprocess``) decodes only the
+    proposals that survive post-processing: post-processing then runs BETWEEN the detector and the
+    captioner -- it reads the detector's outputs only -- and its ``pred_mask``, a superset of what ``predictions`` and
+    ``caption_eval`` read, becomes the captioner's ``decode_mask``; the same post-processing tensors serve the rest of the call
+    (it runs once).  ``pred_*``, ``post_*`` and the caption metrics are those of ``"all"``; ``lang_cap`` holds the empty caption
+    where nothing was decoded, and the forward also returns ``lang_cap_decoded`` and ``lang_cap_rows``.  ``decode_capacity``:
+    None sizes the decoder's row list to the number of kept proposals (one 4-byte device-to-host read per call); an int in
+    1..B K fixes it (no host read; kept proposals beyond it, in (scene, proposal) order, are not decoded)."""
 
     def __init__(self, model, graph=True, postprocess=None, detection_ap=None, caption_eval=None, predictions=None, beam_size=None,
-                 length_penalty=None, sample=None):
+                 length_penalty=None, sample=None, decode="all", decode_capacity=None):
         self.model = model
+        if decode not in ("all", "kept"):
+            raise ValueError(f"Evaluator: decode {decode!r} must be 'all' or 'kept'")
+        if decode == "kept" and postprocess is None:
+            raise ValueError("Evaluator: decode='kept' needs postprocess")
+        if decode_capacity is not None and (isinstance(decode_capacity, bool) or not isinstance(decode_capacity, int)
+                                            or decode_capacity < 1):
+            raise ValueError(f"Evaluator: decode_capacity {decode_capacity!r} must be None or an int >= 1")
+        self.decode, self.decode_capacity = decode, decode_capacity
         # decoding attributes of the captioner (transformer_captioner.TransformerDecoderModel); None leaves what it has
         cap = getattr(model, "caption", None)
         if beam_size is not None or length_penalty is not None:
@@ -937,11 +954,25 @@ class Evaluator:
         data_dict.pop("_fps_prefetch", None)
         if next_data is not None:
             self.prefetch(next_data)
-        out = self.model(d, is_eval=True)
-        if self.post_kw is not None:
+        if self.decode == "kept":
             from .postprocess import detection_postprocess
-            post = detection_postprocess(out["point_clouds"], out["bbox_corner"], out["objectness_scores"], out["sem_cls"],
-                                         out["sem_cls_scores"], **self.post_kw)
+            kept = {}
+
+            def after_proposal(dd):   # the detector's outputs exist: post-process now, decode what it keeps
+                kept["post"] = detection_postprocess(dd["point_clouds"], dd["bbox_corner"], dd["objectness_scores"], dd["sem_cls"],
+                                                     dd["sem_cls_scores"], **self.post_kw)
+                dd["decode_mask"], dd["decode_capacity"] = kept["post"]["pred_mask"], self.decode_capacity
+
+            out = self.model(d, is_eval=True, after_proposal=after_proposal)
+        else:
+            out = self.model(d, is_eval=True)
+        if self.post_kw is not None:
+            if self.decode == "kept":
+                post = kept["post"]
+            else:
+                from .postprocess import detection_postprocess
+                post = detection_postprocess(out["point_clouds"], out["bbox_corner"], out["objectness_scores"], out["sem_cls"],
+                                             out["sem_cls_scores"], **self.post_kw)
             for k, v in post.items():
                 if v is not None:
                     out["post_" + k] = v

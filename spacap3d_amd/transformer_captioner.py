@@ -778,8 +778,10 @@ class TransformerDecoderModel(nn.Module):
     sample_seed = None          # an integer: the same draws at every call (forward_eval's sample_seed, when that is None)
     last_sample_trace = None
 
+    last_decode_slot = None     # forward_eval with a decode_mask: int32 (B K,), the packed row of every proposal (-1: not decoded)
+
     def forward_eval(self, ep, use_cache=True, beam_size=None, length_penalty=None, num_samples=None, temperature=None, top_k=None,
-                     sample_seed=None, top_p=None):
+                     sample_seed=None, top_p=None, decode_mask=None, decode_capacity=None):
         """Greedy decoding of B*K captions (:402-453).  The reference re-runs the 6-layer encoder AND the whole
         decoder prefix at each of the 31 steps; the encoder output does not depend on the words (computed once),
         and with ``use_cache`` the decoder keeps the keys / values of earlier positions so that each step only
@@ -800,7 +802,28 @@ class TransformerDecoderModel(nn.Module):
         the first eos) and ``lang_cap_score`` (B, K) its summed log-probability under the model's own distribution;
         ``lang_cap_samples`` (B, K, S, n_words), ``lang_cap_sample_scores`` and ``lang_cap_sample_lengths`` (B, K, S) hold every
         sample.  ``sample_seed``: an integer draws the same captions at every call; None draws new ones per call and, in a
-        captured graph, after every ``attention.advance_rng``."""
+        captured graph, after every ``attention.advance_rng``.
+
+        ``decode_mask`` (B, K) bool or uint8 (default: ``ep["decode_mask"]``; none: everything above, unchanged): decode only
+        the flagged proposals.  The encoder still sees all K tokens; the flagged (scene, proposal) pairs
+        are packed in flat order into a dense row list (``decode_select``), the unchanged decoders run on those rows, and every
+        output above comes back in its usual shape.  A proposal that was not decoded holds the empty caption (eos, then zeros --
+        once per hypothesis / sample), score 0.0 and length 1: the length ``sample_next_kernel`` and ``beam_step_kernel`` /
+        ``beam_finish_kernel`` report for a caption whose first word is eos.  Two more outputs: ``lang_cap_decoded`` bool
+        (B, K), True where the proposal was decoded, and ``lang_cap_rows`` int32 (2,) = the number of flags and the number of
+        them decoded.  ``decode_capacity`` (default: ``ep["decode_capacity"]``):
+
+        * an int in 1..B K -- the row list has that length whatever the mask holds: no value is read back on the host and the
+          call can be captured in a graph.  Flags beyond the capacity, in flat order, are not decoded
+          (``lang_cap_decoded`` is False there, ``lang_cap_rows[0]`` > ``lang_cap_rows[1]``); rows behind the last flag are
+          zero indicator rows, decoded to finite values and dropped;
+        * None -- the exact mode: the row list has the length of the number of flags, read back from the device.  That
+          4-byte device-to-host copy is the one host synchronisation of the feature (the call cannot be captured); no flag set
+          skips the decoder.
+
+        With a mask ``use_cache=False`` raises ``ValueError``.  ``last_beam_trace`` / ``last_sample_trace`` keep the packed-row
+        layout; ``last_decode_slot`` (and the traces' ``"slot"``) maps proposals to rows.  The sampler's noise is keyed by
+        ROW: a fixed ``sample_seed`` repeats the draws for a fixed mask, another mask gives other draws."""
         W = int(self.beam_size if beam_size is None else beam_size)
         alpha = float(self.length_penalty if length_penalty is None else length_penalty)
         if W < 1:
@@ -822,6 +845,10 @@ class TransformerDecoderModel(nn.Module):
             check_arguments("forward_eval", S, tau, topk, self.model.generator.proj.out_features, top_p)
             if not use_cache:
                 raise ValueError("forward_eval: sampling keeps key / value caches (use_cache=False is the greedy parity path)")
+        decode_mask = ep.get("decode_mask") if decode_mask is None else decode_mask
+        if decode_mask is not None:
+            decode_capacity = ep.get("decode_capacity") if decode_capacity is None else decode_capacity
+            decode_mask, decode_capacity = self._check_decode_mask(ep, decode_mask, decode_capacity, use_cache)
         obj_features = ep["aggregated_vote_features"]
         if self.token_proj is not None:
             obj_features = self.token_proj(obj_features)
@@ -839,8 +866,8 @@ class TransformerDecoderModel(nn.Module):
         else:
             memory = self.model.encode(src, src_pos, src_mask)
         obj_flat = obj_features.reshape(B * K, -1)
-        ys = torch.full((B * K, 1), self.word_to_idx["sos"], dtype=torch.long, device=obj_features.device)
         if not use_cache:
+            ys = torch.full((B * K, 1), self.word_to_idx["sos"], dtype=torch.long, device=obj_features.device)
             for _ in range(MAX_DES_LEN + 1):
                 L = ys.size(1) + 1 if self.early_guide else ys.size(1)
                 out = self.model(src, ys, src_mask, subsequent_mask(L, device=ys.device),
@@ -851,11 +878,20 @@ class TransformerDecoderModel(nn.Module):
             return ep
         # -- cached path -----------------------------------------------------------------------------------
         dec = self.model.decoder
-        caches = [dict() for _ in dec.layers]
+        if decode_mask is not None:
+            return self._decode_kept(ep, B, K, dec, obj_flat, memory.reshape(B * K, -1) if memory.shape[0] != B * K else None,
+                                     decode_mask, decode_capacity, W, alpha, beam, S, tau, topk, sample_seed, top_p)
         if memory.shape[0] != B * K:  # encoder ran once per scene: the indicator adds that proposal's memory row
             indicator = obj_flat.unsqueeze(1) + memory.reshape(B * K, -1).unsqueeze(1)
         else:
             indicator = obj_flat.unsqueeze(1)
+        return self._decode_rows(ep, B, K, dec, indicator, W, alpha, beam, S, tau, topk, sample_seed, top_p)
+
+    def _decode_rows(self, ep, B, K, dec, indicator, W, alpha, beam, S, tau, topk, sample_seed, top_p):
+        """The cached decoding of ``forward_eval`` over the B K rows of ``indicator`` (B K, 1, d): sampled, beam or greedy, fused
+        or through the cached per-operator decoder; the outputs go to ``ep`` as (B, K, ...)."""
+        caches = [dict() for _ in dec.layers]
+        ys = torch.full((B * K, 1), self.word_to_idx["sos"], dtype=torch.long, device=indicator.device)
         embed, pos = self.model.tgt_embed[0], self.model.tgt_embed[1]
         cd = getattr(ops(), "caption_decode", None)
         fused = self.early_guide and not self.training and cd is not None \
@@ -891,6 +927,67 @@ class TransformerDecoderModel(nn.Module):
             words = self.model.generator(self._cached_step(dec, caches, indicator, step, words)).argmax(dim=-1)
             ys = torch.cat([ys, words.unsqueeze(1)], dim=1)
         ep["lang_cap"] = ys[:, 1:].view(B, K, -1)
+        return ep
+
+    @staticmethod
+    def _check_decode_mask(ep, mask, capacity, use_cache):
+        """The arguments of decoding under a mask (``forward_eval``), checked before anything runs."""
+        B, K = ep["aggregated_vote_features"].shape[:2]
+        if not use_cache:
+            raise ValueError("forward_eval: decode_mask packs the rows of the cached decoders (use_cache=False is the greedy parity path)")
+        if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (B, K):
+            raise ValueError(f"forward_eval: decode_mask must be a (B, K) = ({B}, {K}) tensor, got "
+                             f"{tuple(mask.shape) if isinstance(mask, torch.Tensor) else type(mask).__name__}")
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"forward_eval: decode_mask must be bool or uint8, got {mask.dtype}")
+        if capacity is not None:
+            if isinstance(capacity, bool) or not isinstance(capacity, int) or not 1 <= capacity <= B * K:
+                raise ValueError(f"forward_eval: decode_capacity {capacity!r} must be None or an int in 1..B K = {B * K}")
+        if not mask.is_cuda:
+            raise RuntimeError("forward_eval: decode_mask: CPU not supported")
+        return mask, capacity
+
+    def _decode_kept(self, ep, B, K, dec, obj_flat, memory_flat, mask, capacity, W, alpha, beam, S, tau, topk, sample_seed, top_p):
+        """``forward_eval`` under a ``decode_mask``: pack the flagged proposals (``decode_select.select``),
+        form the indicator of the packed rows only (``gather``: obj + memory without the B K-row sum), run ``_decode_rows`` on
+        them as one scene of that many proposals, and scatter what it returned back to (B, K, ...)."""
+        from . import decode_select as ds
+        n, eos, L = B * K, self.word_to_idx["eos"], MAX_DES_LEN + 1
+        dev = obj_flat.device
+        rows, slot, count = ds.select(mask, n if capacity is None else capacity)
+        if capacity is None:
+            kept = int(count[:1].cpu()[0])    # the exact mode's host read: 4 bytes, the feature's one synchronisation
+            rows = rows[:kept]
+        else:
+            kept = capacity
+        got = {}
+        if kept > 0:
+            self._decode_rows(got, 1, kept, dec, ds.gather(obj_flat, memory_flat, rows).unsqueeze(1), W, alpha, beam, S, tau, topk,
+                              sample_seed, top_p)
+        else:   # nothing to decode: one row of the right shapes that no slot points at
+            z = lambda *shape, dtype=torch.float32: torch.zeros(1, 1, *shape, dtype=dtype, device=dev)  # noqa: E731
+            got["lang_cap"] = z(L, dtype=torch.long)
+            if S >= 1:
+                got["lang_cap_score"], got["lang_cap_samples"] = z(), z(S, L, dtype=torch.long)
+                got["lang_cap_sample_scores"], got["lang_cap_sample_lengths"] = z(S), z(S, dtype=torch.int32)
+            elif beam:
+                got["lang_cap_score"] = z()
+                if self.beam_return_all:
+                    got["lang_cap_beams"] = z(W, L, dtype=torch.long)
+                    got["lang_cap_beam_scores"], got["lang_cap_beam_lengths"] = z(W), z(W, dtype=torch.int32)
+        for k, t in got.items():
+            t = t[0]                          # (kept, ...)
+            if t.dtype == torch.int64:
+                out = ds.scatter_words(t, slot, eos)
+            else:                             # scores: 0.0; lengths: the empty caption's, 1
+                out = ds.scatter_values(t, slot, 0.0 if t.dtype == torch.float32 else 1)
+            ep[k] = out.view(B, K, *t.shape[1:])
+        ep["lang_cap_decoded"] = (slot >= 0).view(B, K)
+        ep["lang_cap_rows"] = count
+        self.last_decode_slot = slot
+        trace = self.last_sample_trace if S >= 1 else self.last_beam_trace if beam else None
+        if isinstance(trace, dict) and kept > 0:
+            trace["slot"] = slot
         return ep
 
     def _cached_step(self, dec, caches, ind, i, words, parents=None):
