@@ -40,8 +40,8 @@ class _Stack:
         self.V, self.pe, self.pieces = self.gw.shape[0], pe, None
         if tf_layer.FFN_BF3 and rows > tf_layer.FFN_BF3_MIN_ROWS:
             refresh_ffn_pieces(layers)
-            pieces = [tf_layer._FFN_PIECES.get(l.feed_forward.w_1.weight.data_ptr()) for l in layers]
-            self.pieces = [e[1] for e in pieces] if all(e is not None for e in pieces) else None
+            pieces = [tf_layer.ffn_pieces(l.feed_forward.w_1.weight, self.dff) for l in layers]
+            self.pieces = pieces if all(e is not None for e in pieces) else None
 
     def allocate(self, on_cache_oom=None):
         """The key / value caches (rows, T, 128) of every layer -- ``on_cache_oom(error)`` answers a failure to allocate them --

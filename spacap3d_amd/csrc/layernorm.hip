@@ -61,7 +61,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float *__restr
     s1 = spacap::wave_sum(s1);
     s2 = spacap::wave_sum(s2);
     const float sd = 1.0f / r - eps;                       // the unbiased std
-    const float c2 = -(s2 * r * r) / (sd * (float)(D - 1));  // 0/0 = NaN on a constant row, as autograd gives
+    // (a constant row: std == 0, where autograd masks the gradient through the std to zero; unmasked this is 0/0 = NaN)
+    const float c2 = sd == 0.f ? 0.f : -(s2 * r * r) / (sd * (float)(D - 1));
     const float c1 = r * s1 / (float)D;
     float *dr = dx + row * D;
     for (int j = lane; j < D; j += 64)
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_reg_kernel(const float *__r
     s1 = spacap::wave_sum(s1);
     s2 = spacap::wave_sum(s2);
     const float sd = 1.0f / r - eps;
-    const float c2 = -(s2 * r * r) / (sd * (float)(D - 1));
+    const float c2 = sd == 0.f ? 0.f : -(s2 * r * r) / (sd * (float)(D - 1));   // (constant row: as above)
     const float c1 = r * s1 / (float)D;
     float *dr = dx + row * D;
 #pragma unroll

@@ -303,7 +303,8 @@ __global__ __launch_bounds__(256) void tf_rows_kernel(const TfRowsArgs P) {
     s1 = (s_red[0][0][l15] + s_red[0][1][l15]) + (s_red[0][2][l15] + s_red[0][3][l15]);
     s2 = (s_red[1][0][l15] + s_red[1][1][l15]) + (s_red[1][2][l15] + s_red[1][3][l15]);
     const float sdv = 1.0f / r - P.eps;                            // the unbiased std
-    const float c2 = -(s2 * r * r) / (sdv * (float)(D - 1));      // 0/0 = NaN on a constant row, as autograd gives
+    // (a constant row: std == 0, where autograd masks the gradient through the std to zero; unmasked this is 0/0 = NaN)
+    const float c2 = sdv == 0.f ? 0.f : -(s2 * r * r) / (sdv * (float)(D - 1));
     const float c1 = r * s1 / (float)D;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {

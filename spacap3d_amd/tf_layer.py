@@ -128,7 +128,21 @@ class LnQkv(Function):
 # input has more than FFN_BF3_MIN_ROWS rows and falls back to the fp32-MFMA kernel otherwise (few rows: latency bound either way).
 FFN_BF3 = True
 FFN_BF3_MIN_ROWS = 512
-_FFN_PIECES = {}      # w_1.weight.data_ptr() -> (weakref to that parameter, bf16 piece images of the layer)
+_FFN_PIECES = {}      # w_1.weight.data_ptr() -> (weakref to that parameter, its d_ff, bf16 piece images of the layer)
+
+
+def ffn_pieces(w1, dff):
+    """The split-bf16 images registered for THIS ``w_1`` weight and feed-forward width, or None.  An entry answers only while its
+    parameter is alive, still lives at the address it was registered under (an optimizer that flattens its parameters moves
+    them, and the old address is then free for any other (dff, 128) tensor) and was split at the caller's width."""
+    ent = _FFN_PIECES.get(w1.data_ptr())
+    if ent is None:
+        return None
+    ref, ent_dff, images = ent
+    w = ref()
+    if w is None or w.data_ptr() != w1.data_ptr() or ent_dff != int(dff):
+        return None
+    return images
 
 
 def refresh_ffn_pieces(layers):
@@ -154,10 +168,10 @@ def refresh_ffn_pieces(layers):
     check(lib.spacap_tf_ffn_split_f32(arr(*[w.data_ptr() for w in w1s]), arr(*[w.data_ptr() for w in w2s]),
                                       arr(*[buf[i].data_ptr() for i in range(n)]), n, dff, torch.cuda.current_stream(dev).cuda_stream),
           "spacap_tf_ffn_split_f32")
-    for dead in [k for k, (ref, _) in _FFN_PIECES.items() if ref() is None]:
+    for dead in [k for k, (ref, _, _) in _FFN_PIECES.items() if ref() is None or ref().data_ptr() != k]:
         del _FFN_PIECES[dead]
     for i, w in enumerate(w1s):
-        _FFN_PIECES[w.data_ptr()] = (weakref.ref(w), buf[i])
+        _FFN_PIECES[w.data_ptr()] = (weakref.ref(w), dff, buf[i])
 
 
 def _ffn(mode, x2, Wa, Wb, bias, y, dff, p, seed, dev):
@@ -167,9 +181,9 @@ def _ffn(mode, x2, Wa, Wb, bias, y, dff, p, seed, dev):
     st = torch.cuda.current_stream(dev).cuda_stream
     rs = rng_state(dev).data_ptr() if (p > 0.0 and mode == 0) else None
     w1 = Wa if mode == 0 else Wb
-    ent = _FFN_PIECES.get(w1.data_ptr()) if (FFN_BF3 and R > FFN_BF3_MIN_ROWS) else None
-    if ent is not None and ent[0]() is not None:
-        check(lib.spacap_tf_ffn_bf3_f32(mode, x2.data_ptr(), ent[1].data_ptr(), _p(bias), _p(y), R, dff, float(p), int(seed), rs,
+    images = ffn_pieces(w1, dff) if (FFN_BF3 and R > FFN_BF3_MIN_ROWS) else None
+    if images is not None:
+        check(lib.spacap_tf_ffn_bf3_f32(mode, x2.data_ptr(), images.data_ptr(), _p(bias), _p(y), R, dff, float(p), int(seed), rs,
                                         hid.data_ptr(), parts.data_ptr(), st), "spacap_tf_ffn_bf3_f32")
         return hid, parts
     check(lib.spacap_tf_ffn_f32(mode, x2.data_ptr(), Wa.data_ptr(), Wb.data_ptr(), _p(bias), _p(y), R, dff, float(p), int(seed),

@@ -169,6 +169,37 @@ def test_fused_layernorm_matches_reference_formula(att, shape):
     assert torch.equal(y2, y)
 
 
+@pytest.mark.parametrize("D", [128, 300, 1000], ids=["registers-2", "registers-8", "generic"])
+@pytest.mark.parametrize("value", [0.0, 0.75], ids=["zero-row", "row-of-0.75"])
+def test_fused_layernorm_backward_of_a_constant_row_is_finite(att, D, value):
+    """A constant row has std == 0: autograd masks the gradient through the std to zero there and returns the finite
+    r (dxh - mean(dxh)), r = 1 / eps.  Both backward kernels (register-resident and generic) against float64 autograd of the
+    reference formula; the rows around the constant ones are bit-identical to a run without them."""
+    g = torch.Generator().manual_seed(D)
+    x = torch.randn(9, D, generator=g) * 3 + 1
+    a = torch.rand(D, generator=g) + 0.5
+    b = torch.randn(D, generator=g)
+    w = torch.randn(9, D, generator=g)
+    xc = x.clone()
+    xc[2], xc[8] = value, value
+    grads = {}
+    for name, xin in (("plain", x), ("constant", xc)):
+        xg, ag, bg = (t.to(DEV).requires_grad_(True) for t in (xin, a, b))
+        y = att.layer_norm(xg, ag, bg)
+        (y * w.to(DEV)).sum().backward()
+        grads[name] = (y.detach().cpu(), xg.grad.cpu(), ag.grad.cpu(), bg.grad.cpu())
+    xr, ar, br = (t.double().requires_grad_(True) for t in (xc, a, b))
+    (ref.layer_norm(xr, ar, br) * w.double()).sum().backward()
+    y, dx, da, db = grads["constant"]
+    assert torch.isfinite(xr.grad).all() and torch.equal(y[2], b) and torch.equal(y[8], b)
+    print(f"LAYERNORM constant row D={D} value={value}: non-finite dx={int((~torch.isfinite(dx)).sum())} of {dx.numel()}")
+    assert torch.isfinite(dx).all() and torch.isfinite(da).all() and torch.isfinite(db).all()
+    for got, want in ((dx, xr.grad), (da, ar.grad), (db, br.grad)):
+        assert float((got.double() - want).abs().max()) / float(want.abs().max()) < 1e-5
+    keep = [0, 1, 3, 4, 5, 6, 7]
+    assert torch.equal(dx[keep], grads["plain"][1][keep]) and torch.equal(y[keep], grads["plain"][0][keep])
+
+
 @pytest.mark.parametrize("B,H,K,D", [(2, 8, 256, 16), (1, 8, 64, 16), (2, 32, 40, 16), (1, 4, 33, 32)])
 def test_relation_feature_matches_reference_chain(att, B, H, K, D):
     """models/transformer_captioner.py:393-396 (repeat / product / transposes / view) and its autograd backward."""
