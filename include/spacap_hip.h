@@ -1289,6 +1289,23 @@ int spacap_scst_select_f32(const float *xyz, const float *center_label, const fl
                            int G, int M, int n_items, int n_obj, int nkeys, float near2, int64_t *prop, int64_t *obj,
                            int32_t *slot_of, int32_t *key, float *dist, int32_t *n_sel, spacap_stream_t stream);
 
+/* The teacher-forcing rows of cross-entropy training over every matched object of a scene (DESIGN.md section 7o;
+ * csrc/dense_xe.hip).  key i32 [B,M] (spacap_scst_select_f32's); the corpus: ref_tok i32 [n_tok], ref_off / ref_len i32 [n_refs],
+ * key_ref_off i32 [nkeys + 1].  Group g = b M + m: key[g] outside 0..nkeys-1, or a key with n = key_ref_off[key + 1] -
+ * key_ref_off[key] <= 0 references, leaves every row of the group empty.  Otherwise h = hash32(g, make_seed(seed, seed_dev)) of
+ * csrc/dropout.hpp (seed_dev: the optional device-resident step word, NULL = none), j0 = (uint64(h) * n) >> 32, and row s < r of
+ * the group takes reference key_ref_off[key] + (j0 + s) % n when s < n, else it is empty: distinct references inside a group,
+ * every row's marginal uniform up to the 2^-32 rounding of the multiply-shift.  A sentence of len ids becomes T ids: its ids then
+ * zeros (len <= T), or its first T - 1 ids then eos (len > T); an id outside 0..n_vocab-1 becomes unk.  An empty row is sos,
+ * eos, zeros.  Writes, every element: ids i64 [B M r, T]; tok i64 [B M r, T + 1] = 1, then the id row; ref i32 [B M r] the
+ * reference's index or -1; good u8 [B M r]; length i32 [B M r] = min(len, T) - 1 (the target words with eos; not below 0), 0 for
+ * an empty row.  A reference whose offset or length leaves the tables gives an empty row.  One launch, one wave per group, no
+ * atomics, no state: a captured call replays.  B >= 0 (0: a no-op), M >= 1, 1 <= r <= 8, T >= 2, n_vocab >= 1. */
+int spacap_dense_xe_targets_i64(const int32_t *key, int B, int M, const int32_t *ref_tok, int64_t n_tok, const int32_t *ref_off,
+                                const int32_t *ref_len, int64_t n_refs, const int32_t *key_ref_off, int nkeys, int n_vocab, int unk,
+                                int sos, int eos, int r, int T, uint64_t seed, const uint64_t *seed_dev, int64_t *ids, int64_t *tok,
+                                int32_t *ref, uint8_t *good, int32_t *length, spacap_stream_t stream);
+
 /* ---- dense-caption predictions (replaces the host loop a caller of the reference writes over parse_predictions with
  * per_class_proposal=False, lib/ap_helper.py:145-158, and decode_caption, lib/eval_helper.py:46-57; csrc/predictions.hip) --- */
 

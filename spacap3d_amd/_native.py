@@ -110,6 +110,8 @@ SIGNATURES = {
     "spacap_scst_loss_fwd_f32": (_i, [_p] * 6 + [_i] * 4 + [_p] * 5 + [_p]),
     "spacap_scst_loss_bwd_f32": (_i, [_p] * 7 + [_i] * 3 + [_p, _p]),
     "spacap_scst_select_f32": (_i, [_p] * 6 + [_i] * 7 + [_f] + [_p] * 6 + [_p]),
+    "spacap_dense_xe_targets_i64": (_i, [_p, _i, _i, _p, ctypes.c_int64, _p, _p, ctypes.c_int64, _p] + [_i] * 7 + [_u64, _p]
+                                    + [_p] * 5 + [_p]),
     "spacap_dense_caption_select": (_i, [_p] * 5 + [_i] * 5 + [_p] * 7 + [_p]),
     "spacap_decode_select_i32": (_i, [_p, _l, _l, _p, _p, _p] + [_p]),
     "spacap_decode_gather_f32": (_i, [_p, _p, _p, _l, _i, _p] + [_p]),

@@ -615,6 +615,11 @@ class Trainer:
         dev = example["point_clouds"].device
         if dev.type != "cuda":
             return False
+        if getattr(getattr(self.model, "caption", None), "dense_xe", None) is not None:
+            # cross-entropy over every matched object: step() runs it eagerly, as it runs the self-critical
+            # modes; a whole-step capture with it has not been built
+            self.graph_error = "dense_xe: the step is not captured; Trainer.step runs this mode eagerly"
+            return False
         world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         self._graph_with_opt = (world == 1) and not self.split_optimizer
         try:
@@ -800,6 +805,9 @@ class Trainer:
         self.check_health(wait=False)
         try:
             if self.graph is not None:
+                if getattr(getattr(self.model, "caption", None), "dense_xe", None) is not None:
+                    raise RuntimeError("Trainer.step: the captured step holds the plain caption path and dense_xe runs eagerly: "
+                                       "use a Trainer whose step was not captured")
                 return self._graph_step(data_dict, next_data)
             if self.bucket is None:
                 self._setup({k: v for k, v in data_dict.items() if k != "_fps_prefetch"})

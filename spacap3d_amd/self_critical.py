@@ -53,6 +53,48 @@ def reward_weights(reward):
     return w
 
 
+def select_pairs(who, corpus, max_proposals, near2, xyz, center_label, box_label_mask, scene_object_ids, dataset_idx, out=None):
+    """The launch of ``spacap_scst_select_f32`` behind ``SelfCritical.select`` and ``dense_xe.DenseCaptionXE.select`` (arguments
+    and results as stated there); ``who`` names the caller in the refusals, ``near2`` is the float32 square of the threshold."""
+    xyz = gpu(who, xyz, "xyz")
+    dev = xyz.device
+    ctr = gpu(who, center_label, "center_label")
+    msk = gpu(who, box_label_mask, "box_label_mask")
+    ids = gpu(who, scene_object_ids, "scene_object_ids")
+    idx = gpu(who, dataset_idx, "dataset_idx").reshape(-1)
+    M = int(max_proposals)
+    if xyz.dim() != 3 or xyz.shape[-1] != 3 or ctr.dim() != 3 or ctr.shape[-1] != 3 or ctr.shape[0] != xyz.shape[0] or \
+            tuple(msk.shape) != tuple(ctr.shape[:2]) or tuple(ids.shape) != tuple(ctr.shape[:2]) or idx.numel() != xyz.shape[0]:
+        raise RuntimeError(f"{who}: expected xyz (B,K,3), center_label (B,G,3), box_label_mask / scene_object_ids (B,G), "
+                           f"dataset_idx (B,); got {tuple(xyz.shape)}, {tuple(ctr.shape)}, {tuple(msk.shape)}, {tuple(ids.shape)}, "
+                           f"{tuple(idx.shape)}")
+    B, K, G = xyz.shape[0], xyz.shape[1], ctr.shape[1]
+    if any(t.device != dev for t in (ctr, msk, ids, idx)):
+        raise RuntimeError(f"{who}: xyz lives on {dev}, the labels elsewhere")
+    if not (K >= 1 and M <= G <= MAX_OBJECTS):
+        raise RuntimeError(f"{who}: K={K} proposals, G={G} object slots, max_proposals={M}: supported K >= 1, "
+                           f"max_proposals <= G <= {MAX_OBJECTS}")
+    xyz, ctr, msk = (t.detach().float().contiguous() for t in (xyz, ctr, msk))
+    ids, idx = ids.long().contiguous(), idx.long().contiguous()
+    kt = corpus.on(dev)["key_table"]
+    with torch.cuda.device(dev):
+        if out is None:
+            out = (torch.empty(B, M, dtype=torch.int64, device=dev), torch.empty(B, M, dtype=torch.int64, device=dev),
+                   torch.empty(B, M, dtype=torch.int32, device=dev), torch.empty(B, M, dtype=torch.int32, device=dev),
+                   torch.empty(B, M, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+        want = (((B, M), torch.int64), ((B, M), torch.int64), ((B, M), torch.int32), ((B, M), torch.int32),
+                ((B, M), torch.float32), ((B,), torch.int32))
+        for t, (shape, dtype) in zip(out, want):
+            if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+                raise RuntimeError(f"{who}: out must be contiguous {want} on {dev}")
+        prop, obj, slot_of, key, dist, n_sel = out
+        check(lib.spacap_scst_select_f32(xyz.data_ptr(), ctr.data_ptr(), msk.data_ptr(), ids.data_ptr(), idx.data_ptr(),
+                                         kt.data_ptr(), B, K, G, M, kt.shape[0], kt.shape[1], corpus.nkeys, float(near2),
+                                         prop.data_ptr(), obj.data_ptr(), slot_of.data_ptr(), key.data_ptr(), dist.data_ptr(),
+                                         n_sel.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "spacap_scst_select_f32")
+    return prop, obj, slot_of, key, dist, n_sel
+
+
 class SelfCritical:
     """``SelfCritical(corpus, sos, eos, num_samples=5, temperature=1.0, top_k=0, baseline="greedy", seed=None, top_p=None)``.
 
@@ -124,43 +166,8 @@ class SelfCritical:
         six tensors of ``out`` when given.  One launch on the current stream, no host synchronisation."""
         if self.proposals != "matched":
             raise RuntimeError("self_critical: select() belongs to proposals='matched'")
-        xyz = gpu("self_critical", xyz, "xyz")
-        dev = xyz.device
-        ctr = gpu("self_critical", center_label, "center_label")
-        msk = gpu("self_critical", box_label_mask, "box_label_mask")
-        ids = gpu("self_critical", scene_object_ids, "scene_object_ids")
-        idx = gpu("self_critical", dataset_idx, "dataset_idx").reshape(-1)
-        M = self.max_proposals
-        if xyz.dim() != 3 or xyz.shape[-1] != 3 or ctr.dim() != 3 or ctr.shape[-1] != 3 or ctr.shape[0] != xyz.shape[0] or \
-                tuple(msk.shape) != tuple(ctr.shape[:2]) or tuple(ids.shape) != tuple(ctr.shape[:2]) or idx.numel() != xyz.shape[0]:
-            raise RuntimeError(f"self_critical: expected xyz (B,K,3), center_label (B,G,3), box_label_mask / scene_object_ids (B,G), "
-                               f"dataset_idx (B,); got {tuple(xyz.shape)}, {tuple(ctr.shape)}, {tuple(msk.shape)}, {tuple(ids.shape)}, "
-                               f"{tuple(idx.shape)}")
-        B, K, G = xyz.shape[0], xyz.shape[1], ctr.shape[1]
-        if any(t.device != dev for t in (ctr, msk, ids, idx)):
-            raise RuntimeError(f"self_critical: xyz lives on {dev}, the labels elsewhere")
-        if not (K >= 1 and M <= G <= MAX_OBJECTS):
-            raise RuntimeError(f"self_critical: K={K} proposals, G={G} object slots, max_proposals={M}: supported K >= 1, "
-                               f"max_proposals <= G <= {MAX_OBJECTS}")
-        xyz, ctr, msk = (t.detach().float().contiguous() for t in (xyz, ctr, msk))
-        ids, idx = ids.long().contiguous(), idx.long().contiguous()
-        kt = self.corpus.on(dev)["key_table"]
-        with torch.cuda.device(dev):
-            if out is None:
-                out = (torch.empty(B, M, dtype=torch.int64, device=dev), torch.empty(B, M, dtype=torch.int64, device=dev),
-                       torch.empty(B, M, dtype=torch.int32, device=dev), torch.empty(B, M, dtype=torch.int32, device=dev),
-                       torch.empty(B, M, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
-            want = (((B, M), torch.int64), ((B, M), torch.int64), ((B, M), torch.int32), ((B, M), torch.int32),
-                    ((B, M), torch.float32), ((B,), torch.int32))
-            for t, (shape, dtype) in zip(out, want):
-                if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
-                    raise RuntimeError(f"self_critical: out must be contiguous {want} on {dev}")
-            prop, obj, slot_of, key, dist, n_sel = out
-            check(lib.spacap_scst_select_f32(xyz.data_ptr(), ctr.data_ptr(), msk.data_ptr(), ids.data_ptr(), idx.data_ptr(),
-                                             kt.data_ptr(), B, K, G, M, kt.shape[0], kt.shape[1], self.corpus.nkeys, self.near2,
-                                             prop.data_ptr(), obj.data_ptr(), slot_of.data_ptr(), key.data_ptr(), dist.data_ptr(),
-                                             n_sel.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "spacap_scst_select_f32")
-        return prop, obj, slot_of, key, dist, n_sel
+        return select_pairs("self_critical", self.corpus, self.max_proposals, self.near2, xyz, center_label, box_label_mask,
+                            scene_object_ids, dataset_idx, out)
 
     def rewards(self, tokens, dataset_idx, object_id, rows_per_scene=1, out=None, terms=False):
         """The reward of every drawn caption: ``tokens`` (rows, L) decoded words (any integer dtype), row r of scene

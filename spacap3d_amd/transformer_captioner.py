@@ -444,8 +444,14 @@ class TransformerDecoderModel(nn.Module):
         src_mask = ep["bbox_mask"].unsqueeze(1)
         x0 = out_full = None
         scst = self.self_critical if self.training else None
+        dxe = self.dense_xe if self.training else None
+        if dxe is not None and scst is not None:
+            raise ValueError("dense_xe and self_critical are both set: one training mode at a time")
         if scst is not None and prep is None:
             raise RuntimeError("self_critical: CPU tensors, a backend without caption_prep, the late guide and a captioner without "
+                               "the Transformer encoder are not supported")
+        if dxe is not None and prep is None:
+            raise RuntimeError("dense_xe: CPU tensors, a backend without caption_prep, the late guide and a captioner without "
                                "the Transformer encoder are not supported")
         if prep is not None:
             # encoder first, then nearest proposal + object indicator + token embedding + positional encoding + dropout + mask
@@ -455,6 +461,8 @@ class TransformerDecoderModel(nn.Module):
                 self._relation_head_forked(ep)
             if scst is not None:
                 return self._self_critical_train(ep, scst, prep, src, memory)
+            if dxe is not None:
+                return self._dense_xe_train(ep, dxe, prep, src, memory)
             te = self.model.tgt_embed
             got = prep(ep["aggregated_vote_xyz"], ep["ref_center_label"], src, memory, ep["lang_label"], te[0], te[1])
             if got is not None:
@@ -715,6 +723,52 @@ class TransformerDecoderModel(nn.Module):
         ep["scst_advantage"], ep["scst_logp"] = adv.view(B, M, S), rowlogp.view(B, M, S)
         ep["scst_sample_scores"] = score.view(B, M, S)
         ep["scst_stats"] = out.detach()
+        return ep
+
+    # Cross-entropy training over every matched object of a scene: None = off, else a
+    # dense_xe.DenseCaptionXE.  A plain attribute, not in the state dict; read in training mode only.
+    dense_xe = None
+
+    def _dense_xe_train(self, ep, dx, prep, src, memory):
+        """The captioner's part of a cross-entropy step over every matched object of a scene, after the encoder and the relation
+        head: ``dx.select`` pairs up to M annotated objects per scene with their nearest proposals, ``dx.targets`` draws r of each
+        object's reference sentences as teacher-forcing rows, ``caption_prep_rows`` reads the encoder rows by index (a proposal
+        matched by two objects gets the sum of both gradients from one launch), and the decoder, the vocabulary projection and
+        the plain caption loss run over the B M r rows in the place of the B scenes; a row without a sentence is the empty
+        caption and counts for nothing.  No value is read back on the host."""
+        for k in ("center_label", "box_label_mask", "scene_object_ids", "dataset_idx", "ref_center_label"):
+            if k not in ep:
+                raise KeyError(f"dense_xe: the batch has no {k!r}")
+        prep_rows = getattr(ops(), "caption_prep_rows", None)
+        loss_op = getattr(ops(), "caption_head_loss", None)
+        vp = getattr(ops(), "vocab_projection", None)
+        te, dec, gen = self.model.tgt_embed, self.model.decoder, self.model.generator
+        B = src.shape[0]
+        M, r = dx.max_proposals, dx.refs_per_object
+        with torch.no_grad():
+            # match_idx / pred_ious / good_bbox_masks keep their meaning: the referred object's nearest proposal
+            got = prep(ep["aggregated_vote_xyz"], ep["ref_center_label"], src, memory,
+                       torch.ones(B, 2, dtype=torch.int64, device=src.device), te[0], te[1])
+            if got is None or prep_rows is None or loss_op is None or vp is None:
+                raise RuntimeError("dense_xe: these tensors are not supported by the fused caption path")
+            _, _, idx, _, good, pred_ious = got
+            prop, obj, _, key, _, _ = dx.select(ep["aggregated_vote_xyz"], ep["center_label"], ep["box_label_mask"],
+                                                ep["scene_object_ids"], ep["dataset_idx"])
+            tok, ids, ref, row_good, length = dx.targets(key)
+        got = prep_rows(src, memory, prop, tok, te[0], te[1], r)
+        if got is None:
+            raise RuntimeError("dense_xe: these tensors are not supported by the fused caption path")
+        x0, m8 = got
+        out_full = dec(x0, None, None, m8)
+        logits = vp(out_full, gen.proj, 1)
+        if logits is None:
+            raise RuntimeError("dense_xe: this decoder output is not supported by the fused vocabulary projection")
+        _, cl, ca, _ = loss_op(logits, ids, row_good)
+        ep["_cap_loss"] = (cl, ca)
+        ep["match_idx"], ep["pred_ious"], ep["good_bbox_masks"] = idx, pred_ious, good
+        ep["dense_proposal"], ep["dense_object_id"], ep["dense_key"] = prop, obj, key
+        ep["dense_ref"], ep["dense_count"], ep["dense_length"] = ref.view(B, M, r), row_good.view(B, M, r).bool(), length.view(B, M, r)
+        ep["dense_lang_ids"] = ids.view(B, M, r, ids.shape[1])
         return ep
 
     # The relation head reads the last encoder layer only and the decoder reads the encoder's output only: the two are independent
