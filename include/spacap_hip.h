@@ -998,6 +998,42 @@ int spacap_sample_word_nucleus_f32(const float *x, const void *Wp, const float *
                                    const float *pe_row, int64_t *ys, float *score, int32_t *length, int32_t *finished, float *xw,
                                    void *workspace, spacap_stream_t stream);
 
+/* ---- constrained decoding (restated by tests/decode_constraints_restated.py).  Before a step's word
+ * choice looks at the logits z of a row they become z': every distinct word of the row's history y_0 .. y_{step-1} is
+ * penalised (z / theta when z > 0, else z * theta; one fp32 operation), then the banned words go to -inf: bad_words, eos while
+ * step < min_length, and with n = no_repeat_ngram >= 1 every v for which (y_{step-n+1} .. y_{step-1}, v) already occurs in
+ * the history (n = 1: every used word; nothing while step < n - 1).
+ * spacap_decode_constraints writes a row's two sets as bit images over the vocabulary, bits u32 [rows][2][nw] with
+ * nw = 2 * ceil(V / 64): plane 0 "banned", plane 1 "seen"; bit v % 32 of word v / 32.  rows = R * W; bits holds
+ * spacap_decode_constraints_bytes(rows, V) bytes.  The history is ys i64 [rows][ys_ld], columns 0 .. step - 1 (greedy and
+ * sampled decoding; W = 1), or -- ys null -- a beam hypothesis' own ancestry: word j is trace_word[j][r][slot] (i32
+ * [n_words][R][W], spacap_beam_step_f32's) with slot = anc[r * W + w][j + 2] for j + 2 <= step and w itself behind that (anc
+ * i8 [R * W][T]: the ancestor table of position step + 1; an entry outside 0..W-1 reads w).  A history word outside 0..V-1
+ * counts as none: it sets no bit and matches nothing in an n-gram.  bad_words: i32 [n_bad] in HOST memory, n_bad <= 64, read during the call (nothing to upload: the call can
+ * be captured in a graph).  Refused: step > 31 or step + 1 >= T, T > 32,
+ * n_bad + step + 1 >= V (a row could be left without an allowed word).  Plain stores, no atomics; graph-capturable.
+ * The *_constrained_f32 entry points are the word choices above over z': the same arguments plus bits and theta (finite,
+ * >= 1; 1 = no penalty), the same workspaces, outputs and row-state rules.  log-probabilities are log_softmax(z'); a banned
+ * word is never chosen and never listed (a row with fewer than W allowed words ends its list with -inf entries).  No logits
+ * reach device memory except in the nucleus mode, whose image is patched in place. */
+size_t spacap_decode_constraints_bytes(long rows, int V);
+int spacap_decode_constraints(const int64_t *ys, int ys_ld, const int32_t *trace_word, const int8_t *anc, long R, int W, int T, int V,
+                              int step, int eos, int min_length, int no_repeat_ngram, const int32_t *bad_words, int n_bad, uint32_t *bits,
+                              spacap_stream_t stream);
+int spacap_decode_word_constrained_f32(const float *x, const void *W, const float *bias, long R, int V, const uint32_t *bits, float theta,
+                                       const float *lut, float scale, const float *pe_row, int64_t *ys, int ys_ld, int t_out, float *x_next,
+                                       void *workspace, spacap_stream_t stream);
+int spacap_beam_topw_constrained_f32(const float *x, const void *Wp, const float *bias, long rows, int V, int W, const uint32_t *bits,
+                                     float theta, float *top_logp, int32_t *top_word, void *workspace, spacap_stream_t stream);
+int spacap_sample_word_constrained_f32(const float *x, const void *Wp, const float *bias, long rows, int V, int top_k, float inv_tau,
+                                       uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos, const uint32_t *bits,
+                                       float theta, const float *lut, float scale, const float *pe_row, int64_t *ys, float *score,
+                                       int32_t *length, int32_t *finished, float *xw, void *workspace, spacap_stream_t stream);
+int spacap_sample_word_nucleus_constrained_f32(const float *x, const void *Wp, const float *bias, long rows, int V, float top_p, float inv_tau,
+                                               uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos, const uint32_t *bits,
+                                               float theta, const float *lut, float scale, const float *pe_row, int64_t *ys, float *score,
+                                               int32_t *length, int32_t *finished, float *xw, void *workspace, spacap_stream_t stream);
+
 /* ---- caption decoding over the kept proposals only (csrc/decode_select.hip, restated by
  * tests/decode_select_restated.py).  The decoders above take any number of independent rows; these entry points pack the
  * flagged (scene, proposal) pairs into a dense row list, read the indicator rows through it and put the results back.  Every

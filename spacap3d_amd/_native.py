@@ -256,6 +256,14 @@ SIGNATURES = {
     "spacap_sample_word_f32": (_i, [_p, _p, _p, _l, _i, _i, _f, _u64, _p, _i, _i, _i, _p, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
     "spacap_sample_word_nucleus_workspace_bytes": (ctypes.c_size_t, [_l, _i]),
     "spacap_sample_word_nucleus_f32": (_i, [_p, _p, _p, _l, _i, _f, _f, _u64, _p, _i, _i, _i, _p, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "spacap_decode_constraints_bytes": (ctypes.c_size_t, [_l, _i]),
+    "spacap_decode_constraints": (_i, [_p, _i, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p]),
+    "spacap_decode_word_constrained_f32": (_i, [_p, _p, _p, _l, _i, _p, _f, _p, _f, _p, _p, _i, _i, _p, _p, _p]),
+    "spacap_beam_topw_constrained_f32": (_i, [_p, _p, _p, _l, _i, _i, _p, _f, _p, _p, _p, _p]),
+    "spacap_sample_word_constrained_f32": (_i, [_p, _p, _p, _l, _i, _i, _f, _u64, _p, _i, _i, _i, _p, _f, _p, _f, _p, _p, _p, _p, _p, _p, _p,
+                                                _p]),
+    "spacap_sample_word_nucleus_constrained_f32": (_i, [_p, _p, _p, _l, _i, _f, _f, _u64, _p, _i, _i, _i, _p, _f, _p, _f, _p, _p, _p, _p, _p,
+                                                        _p, _p, _p]),
     "spacap_tf_gemm_splits": (_i, [_l, _i, _i]),
     "spacap_tf_gemm_f32": (_i, [_p, _p, _l, _i, _i, _i, _i, _p, _p]),
     "spacap_tf_dgrad_mask_f32": (_i, [_p, _p, _p, _f, _l, _i, _i, _p, _p]),

@@ -30,14 +30,20 @@ def select_top(cand, W):
 
 
 @torch.no_grad()
-def beam_search(step_fn, R, W, n_words, sos, eos, length_penalty=0.0, device=None):
+def beam_search(step_fn, R, W, n_words, sos, eos, length_penalty=0.0, device=None, constraints=None):
     """``step_fn(s, words, parents)`` returns the (R W, V) log-probabilities of word s of every hypothesis (row r W + w):
     ``words`` (R W,) int64 are the newest words (``sos`` at s = 0) and ``parents`` (R W,) int64 the ROW each hypothesis
     continues (None at s = 0: all W rows of a sequence are the same start) -- a cached decoder reorders its caches with
     ``index_select(0, parents)``.  Returns a dict: ``ys`` (R, n_words) int64 and ``score`` (R,) float32 of the winners,
     ``beams`` (R, W, n_words), ``scores`` (R, W), ``lengths`` (R, W) of all final hypotheses, the trace ``parent`` /
-    ``word`` (n_words, R, W) and ``gap`` (n_words, R): the W-th kept score minus the best one not kept (inf when none)."""
+    ``word`` (n_words, R, W) and ``gap`` (n_words, R): the W-th kept score minus the best one not kept (inf when none).
+    ``constraints``: a ``decode_constraints.DecodeConstraints``.  ``step_fn`` must then return the
+    LOGITS -- the repetition penalty depends on their sign --; they are constrained over each hypothesis' own history, kept
+    here through the parent selections, and the log-softmax is taken of the result."""
+    from . import decode_constraints as dc
     W, n_words, sos, eos = int(W), int(n_words), int(sos), int(eos)
+    cons = dc.resolve(constraints)
+    hist = None
     words = torch.full((R * W,), sos, dtype=torch.long, device=device)
     parents = None
     score = fin = length = None
@@ -47,6 +53,11 @@ def beam_search(step_fn, R, W, n_words, sos, eos, length_penalty=0.0, device=Non
         dev, V = logp.device, logp.shape[1]
         if W > V:
             raise ValueError(f"beam_search: beam width {W} exceeds the vocabulary size {V}")
+        if cons is not None:
+            if hist is None:
+                cons.check("beam_search", V, n_words, eos)
+                hist = torch.zeros(R * W, n_words, dtype=torch.long, device=dev)
+            logp = torch.log_softmax(dc.apply(cons, logp, hist, s, eos), 1)
         if score is None:
             score = torch.full((R, W), NEG_INF, dtype=torch.float32, device=dev)
             score[:, 0] = 0.0
@@ -69,6 +80,9 @@ def beam_search(step_fn, R, W, n_words, sos, eos, length_penalty=0.0, device=Non
         tr_word.append(word)
         words = word.reshape(-1)
         parents = (torch.arange(R, device=dev).unsqueeze(1) * W + parent).reshape(-1)
+        if hist is not None:
+            hist = hist.index_select(0, parents)
+            hist[:, s] = words
     alpha = float(length_penalty)
     norm = score.double() if alpha == 0.0 else score.double() / length.clamp(min=1).double() ** alpha
     best = norm.argmax(1, keepdim=True)                               # (the first maximum: the smaller slot on ties)

@@ -98,19 +98,52 @@ class _Stack:
         return n
 
 
+class _Constrained:
+    """An active ``DecodeConstraints`` for one decoding call over ``rows`` rows: the rows' two bit images
+    over the vocabulary and the launch that refreshes them before a step's word choice."""
+
+    def __init__(self, who, c, rows, V, n_words, eos, dev):
+        import ctypes
+        if eos is None:
+            raise ValueError(f"{who}: constraints need eos")
+        c.check(who, V, n_words, eos)
+        self.theta, self.eos, self.V, self.T = c.repetition_penalty, int(eos), V, n_words + 1
+        self.min_length, self.ngram, self.n_bad = c.min_length, c.no_repeat_ngram, len(c.bad_words)
+        self.bad = (ctypes.c_int32 * max(self.n_bad, 1))(*c.bad_words)
+        self.images = torch.empty(int(lib.spacap_decode_constraints_bytes(rows, V)), dtype=torch.uint8, device=dev)
+        self.bits = self.images.data_ptr()
+
+    def refresh(self, step, R, st, ys=None, trace_word=None, anc=None, W=1):
+        """the images of step ``step``: from the rows of ``ys`` (R, n_words), or a beam's trace and ancestor table"""
+        check(lib.spacap_decode_constraints(None if ys is None else ys.data_ptr(), 0 if ys is None else ys.shape[1],
+                                            None if trace_word is None else trace_word.data_ptr(), None if anc is None else anc.data_ptr(),
+                                            R, W, self.T, self.V, step, self.eos, self.min_length, self.ngram, self.bad, self.n_bad,
+                                            self.bits, st), "spacap_decode_constraints")
+
+
+def _constrained(who, constraints, rows, V, n_words, eos, dev):
+    from .decode_constraints import resolve
+    c = resolve(constraints)
+    return None if c is None else _Constrained(who, c, rows, V, n_words, eos, dev)
+
+
 @torch.no_grad()
-def greedy_decode(dec, generator, embed, pe, indicator, sos, n_words):
+def greedy_decode(dec, generator, embed, pe, indicator, sos, n_words, eos=None, constraints=None):
     """Greedy decoding of R sequences through the early-guide decoder stack ``dec`` with pre-allocated key / value caches
     (models/transformer_captioner.py:402-453; the reference re-runs encoder and decoder prefix for every word).  Position 0
     is the object indicator token (R, 128), position 1 the start symbol, then every chosen word is fed back; one token per
     sequence per step, four launches per layer and step (the training kernels with dropout off + spacap_decode_attn_f32).
     The word choice of a step -- vocabulary projection + arg-max + the chosen word's embedding row -- is one library call
     (csrc/caption_decode.hip: vocab_argmax_kernel / decode_next_kernel: no logits in HBM, no BLAS call).
+    ``constraints`` (a ``decode_constraints.DecodeConstraints`` or a dict of its arguments; needs ``eos``): the word choice
+    over the constrained logits -- one more small launch per step builds the rows' bit images, and the
+    constrained copy of the arg-max kernel tests two bits per logit.  None or nothing active: exactly the calls above.
     Returns the (R, n_words) int64 word ids."""
     R, dev = indicator.shape[0], indicator.device
     T = n_words + 1
     s = _Stack(dec, generator, embed, pe, R, T, dev)
     st, V = s.st, s.V
+    con = _constrained("greedy_decode", constraints, R, V, n_words, eos, dev)
 
     def attn(i, t):
         check(lib.spacap_decode_attn_f32(s.qkv.data_ptr(), s.kc[i].data_ptr(), s.vc[i].data_ptr(), R, s.h, s.dk, T, t, s.scale,
@@ -127,7 +160,13 @@ def greedy_decode(dec, generator, embed, pe, indicator, sos, n_words):
             elif t > 1:
                 x = s.xw
             n = s.position(x, t, attn)
-            if t >= 1:
+            if t >= 1 and con is not None:
+                con.refresh(t - 1, R, st, ys=ys)
+                check(lib.spacap_decode_word_constrained_f32(n.data_ptr(), s.gwp.data_ptr(), s.gb.data_ptr(), R, V, con.bits, con.theta,
+                                                             s.lut.data_ptr(), s.sqrt_d, s.pe_rows[min(t, T - 1)].data_ptr(), ys.data_ptr(),
+                                                             n_words, t - 1, s.xw.data_ptr(), ws.data_ptr(), st),
+                      "spacap_decode_word_constrained_f32")
+            elif t >= 1:
                 # ys[:, t - 1] = argmax_v (n W^T + b); xw = lut[word] sqrt(d) + pe[t]: the input of step t + 1
                 check(lib.spacap_decode_word_f32(n.data_ptr(), s.gwp.data_ptr(), s.gb.data_ptr(), R, V, s.lut.data_ptr(), s.sqrt_d,
                                                  s.pe_rows[min(t, T - 1)].data_ptr(), ys.data_ptr(), n_words, t - 1, s.xw.data_ptr(),
@@ -136,7 +175,8 @@ def greedy_decode(dec, generator, embed, pe, indicator, sos, n_words):
 
 
 @torch.no_grad()
-def beam_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, beam_size, length_penalty=0.0, return_all=False, trace=None):
+def beam_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, beam_size, length_penalty=0.0, return_all=False, trace=None,
+                constraints=None):
     """Beam-search decoding of R sequences with ``beam_size`` = W hypotheses each (1 <= W <= 8): the ``greedy_decode`` loop at
     R W rows (row r W + w = hypothesis w of sequence r) through the same row / feed-forward kernels -- they are
     row-independent -- with three kernels of csrc/caption_decode.hip in place of the greedy ones: attention that reads a
@@ -146,7 +186,8 @@ def beam_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, beam_si
     call can be captured in a graph like the greedy loop.  Cache memory: 12 R W T 512 bytes for 6 layers.
     Returns ``(ys (R, n_words) int64, score (R,) float32)`` -- the winner's words (eos repeats after the first eos) and its
     sum of log-probabilities -- and with ``return_all`` also ``(beams (R, W, n_words) int64, scores (R, W), lengths (R, W))``.  ``trace``: a dict that
-    receives the selections, ``parent`` int8 and ``word`` int32, each (n_words, R, W)."""
+    receives the selections, ``parent`` int8 and ``word`` int32, each (n_words, R, W).  ``constraints``: as for
+    ``greedy_decode``; a hypothesis' history is its own ancestry, read through the trace and the ancestor table."""
     R, dev = indicator.shape[0], indicator.device
     W = int(beam_size)
     T = n_words + 1
@@ -156,6 +197,7 @@ def beam_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, beam_si
     RW = R * W
     s = _Stack(dec, generator, embed, pe, RW, T, dev)
     st = s.st
+    con = _constrained("beam_decode", constraints, RW, V, n_words, eos, dev)
     with torch.cuda.device(dev):
         def cache_oom(e):
             nl = len(s.layers)
@@ -191,9 +233,15 @@ def beam_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, beam_si
             if t >= 1:
                 # the W best (log-probability, word) of every row, then one selection per sequence: state t % 2 -> (t + 1) % 2,
                 # trace[t - 1], the ancestor table for position t + 1 and xw = lut[word] sqrt(d) + pe[t], the input of step t + 1
-                check(lib.spacap_beam_topw_f32(n.data_ptr(), s.gwp.data_ptr(), s.gb.data_ptr(), RW, V, W, top_lp.data_ptr(), top_wd.data_ptr(),
-                                               ws.data_ptr(), st), "spacap_beam_topw_f32")
                 i0, i1 = t % 2, (t + 1) % 2
+                if con is None:
+                    check(lib.spacap_beam_topw_f32(n.data_ptr(), s.gwp.data_ptr(), s.gb.data_ptr(), RW, V, W, top_lp.data_ptr(),
+                                                   top_wd.data_ptr(), ws.data_ptr(), st), "spacap_beam_topw_f32")
+                else:
+                    con.refresh(t - 1, R, st, trace_word=tr_word, anc=anc[i0], W=W)
+                    check(lib.spacap_beam_topw_constrained_f32(n.data_ptr(), s.gwp.data_ptr(), s.gb.data_ptr(), RW, V, W, con.bits, con.theta,
+                                                               top_lp.data_ptr(), top_wd.data_ptr(), ws.data_ptr(), st),
+                          "spacap_beam_topw_constrained_f32")
                 check(lib.spacap_beam_step_f32(top_lp.data_ptr(), top_wd.data_ptr(), R, W, V, T, t, int(eos), score[i0].data_ptr(),
                                                fin[i0].data_ptr(), ln[i0].data_ptr(), score[i1].data_ptr(), fin[i1].data_ptr(),
                                                ln[i1].data_ptr(), anc[i0].data_ptr(), anc[i1].data_ptr(), tr_parent.data_ptr(),
@@ -221,7 +269,7 @@ NUCLEUS_MAX_V = 16384     # spacap_sample_word_nucleus_f32 keeps a row in LDS, 8
 
 @torch.no_grad()
 def sample_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, num_samples=1, temperature=1.0, top_k=0, seed=None,
-                  top_p=None):
+                  top_p=None, constraints=None):
     """Sampled decoding of R sequences, ``num_samples`` = S captions each (the reference decodes greedily
     only): the ``greedy_decode`` loop at R S rows (row r S + s = sample s of sequence r; rows are independent, so the attention is
     the greedy one and there is no ancestor table) with ``spacap_sample_word_f32`` as the word choice: the Gumbel-max draw from
@@ -234,6 +282,8 @@ def sample_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, num_s
     ``sampling.py``) -- the draw is restricted to the words whose strictly more probable words hold less than ``top_p`` of the
     tempered distribution.  This mode alone keeps a step's logits in HBM, R S x (V rounded up to 64) floats, between its two
     launches.  None or 1.0 is the path above, bit for bit; ``top_p`` < 1 with ``top_k`` >= 1 is refused: one restriction at a time.
+    ``constraints``: as for ``greedy_decode``; the softmax, the top-k set, the nucleus and the reported log-probability are
+    those of the constrained logits (the nucleus mode patches its own image of the logits in place).
     Returns ``(ys (R, S, n_words) int64, score (R, S) float32, length (R, S) int32)``: the words (eos repeats after the first
     eos), the summed log-probabilities through the first eos, and the position of the first eos plus one (``n_words``: none);
     or None -- not taken -- for nucleus sampling over more than ``NUCLEUS_MAX_V`` words."""
@@ -250,6 +300,7 @@ def sample_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, num_s
     RS = R * S
     s = _Stack(dec, generator, embed, pe, RS, T, dev)
     st = s.st
+    con = _constrained("sample_decode", constraints, RS, V, n_words, eos, dev)
     if seed is None:
         seed_host, seed_dev = _next_seed(), rng_state(dev).data_ptr()
     else:
@@ -281,7 +332,18 @@ def sample_decode(dec, generator, embed, pe, indicator, sos, eos, n_words, num_s
             elif t > 1:
                 x = s.xw
             n = s.position(x, t, attn)
-            if t >= 1 and p is None:
+            if t >= 1 and con is not None:
+                con.refresh(t - 1, RS, st, ys=ys)
+                tail = (seed_host, seed_dev, n_words, t - 1, int(eos), con.bits, con.theta, s.lut.data_ptr(), s.sqrt_d,
+                        s.pe_rows[min(t, T - 1)].data_ptr(), ys.data_ptr(), score.data_ptr(), length.data_ptr(), fin.data_ptr(),
+                        s.xw.data_ptr(), ws.data_ptr(), st)
+                if p is None:
+                    check(lib.spacap_sample_word_constrained_f32(n.data_ptr(), s.gwp.data_ptr(), s.gb.data_ptr(), RS, V, k, 1.0 / tau, *tail),
+                          "spacap_sample_word_constrained_f32")
+                else:
+                    check(lib.spacap_sample_word_nucleus_constrained_f32(n.data_ptr(), s.gwp.data_ptr(), s.gb.data_ptr(), RS, V, p, 1.0 / tau,
+                                                                         *tail), "spacap_sample_word_nucleus_constrained_f32")
+            elif t >= 1 and p is None:
                 # word t - 1 of every row, its log-probability into the row's state, and xw = lut[word] sqrt(d) + pe[t]
                 check(lib.spacap_sample_word_f32(n.data_ptr(), s.gwp.data_ptr(), s.gb.data_ptr(), RS, V, k, 1.0 / tau, seed_host, seed_dev,
                                                  n_words, t - 1, int(eos), s.lut.data_ptr(), s.sqrt_d,

@@ -17,7 +17,12 @@
 //   vocab_logits_kernel + nucleus_next_kernel : nucleus (top-p) sampling -- the same draw restricted to the words whose strictly
 //       more probable words hold less than p of softmax(logit / tau); the set needs a whole row, so this mode alone writes
 //       the logits to HBM (one image in the workspace) and a workgroup per row reads them back
-// Otherwise no logits reach HBM; no step reads a value back on the host.
+// Otherwise no logits reach HBM; no step reads a value back on the host.  Constrained decoding (restated by
+// tests/decode_constraints_restated.py) -- a minimum length, a no-repeat n-gram rule, bad words, a repetition penalty -- sits at
+// the end of the device code:
+//   decode_constraint_kernel : per step, a row's banned and seen words as two bit images over the vocabulary
+//   vocab_argmax_constrained_kernel, beam_topw_constrained_kernel<WB>, vocab_gumbel_constrained_kernel : the word kernels with two
+//       bit tests per logit; logits_constrain_kernel patches the nucleus mode's image
 //
 // The logit tile -- row split, weight staging, the same six piece products in the same order on the same two accumulators -- the
 // first-maximum compare and the slicing of the vocabulary over workgroups are defined ONCE below: that is what makes a beam of
@@ -843,6 +848,405 @@ __global__ __launch_bounds__(256) void nucleus_next_kernel(const float *__restri
   st4(xw + r * VA_D + 4 * tid, f32x4{e[0] * scale + p[0], e[1] * scale + p[1], e[2] * scale + p[2], e[3] * scale + p[3]});
 }
 
+// ---- constrained decoding (restated by tests/decode_constraints_restated.py) ---------------------------
+// Before a step's word choice looks at the logits z of a row they become z': every word of the row's history is penalised
+// (z / theta when z > 0, else z theta: the CTRL rule), then the banned words -- bad_words, eos before min_length, and the words
+// that would repeat an n-gram of the history -- go to -inf.  A constraint touches at most ~100 logits of a row, so the row's
+// sets travel as two BIT IMAGES over the vocabulary, u32 [rows][2][nw]: plane 0 "banned", plane 1 "seen" (in the history),
+// nw = 2 ceil(V / 64) words, so that a chunk of 64 words is two whole words of each plane.  decode_constraint_kernel builds
+// them once per step; the word kernels below are the kernels above with two bit tests where a lane forms its logit.  The
+// kernels above are not touched (they keep the instruction streams they were measured with); the copies use the same
+// SPACAP_VA_* macros, so the tile arithmetic and the first-maximum rule are the same by construction.
+inline int vc_words(int V) { return 2 * ((V + VA_CHUNK - 1) / VA_CHUNK); }
+constexpr int VC_MAX_BAD = 64, VC_HIST = 31;   // bad words per call; history words of a row (T <= 32 positions)
+struct VcBad { int w[VC_MAX_BAD]; };            // the bad words travel as a kernel argument: no device buffer, nothing to upload
+
+// One wave per row.  The wave's candidates sit in LDS: entries 0..30 the history words y_0 .. y_{step-1} (-1: none), entry
+// 31 eos while step < min_length, entries 32..95 the bad words.  History word y_j is banned by the n-gram rule when
+// j >= n - 1 and (y_{j-n+1} .. y_{j-1}) = (y_{step-n+1} .. y_{step-1}); n = 1 bans every used word.  Then lane l forms image
+// words l, l + 64, ... of both planes from the candidates and stores them: every image word is written once, by one lane,
+// with a plain vector store -- no atomics, the same inputs give the same bits.
+// The history: ys != nullptr: row's words ys[row][0 .. step); else row = r W + w is a beam hypothesis and word j is
+// tr_word[j][r][slot], slot = the cache slot the hypothesis occupied at position j + 2 (where word j was the input):
+// anc[row][j + 2] for j + 2 < t = step + 1, the row's own slot w at position t; an entry outside 0..W-1 reads w, as
+// decode_attn_beam_kernel does.  A word outside 0..V-1 counts as no word: it sets no bit and matches nothing in an n-gram.
+__global__ __launch_bounds__(256) void decode_constraint_kernel(const long long *__restrict__ ys, int ys_ld, const int *__restrict__ tr_word,
+                                                                const signed char *__restrict__ anc, long R, int W, int T, long rows, int V,
+                                                                int step, int eos, int min_length, int ngram, VcBad bad, int n_bad,
+                                                                unsigned *__restrict__ bits, int nw) {
+  __shared__ int s_c[4][VC_HIST + 1 + VC_MAX_BAD];
+  __shared__ int s_f[4][VC_HIST + 1];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long row = (long)blockIdx.x * 4 + wv;
+  const bool live = row < rows;
+  int *c = s_c[wv], *f = s_f[wv];
+  int word = -1;
+  if (live && lane < step) {
+    if (ys != nullptr) {
+      const long long y = ys[(size_t)row * ys_ld + lane];
+      word = y >= 0 && y < V ? (int)y : -1;
+    } else {
+      const long r = row / W;
+      const int w = (int)(row - r * W), p = lane + 2;
+      int slot = w;
+      if (p < step + 1) {
+        const int s = anc[(size_t)row * T + p];
+        slot = (unsigned)s < (unsigned)W ? s : w;
+      }
+      const int y = tr_word[((size_t)lane * R + r) * W + slot];
+      word = (unsigned)y < (unsigned)V ? y : -1;
+    }
+  }
+  if (lane < VC_HIST) c[lane] = word;
+  if (lane == VC_HIST) c[lane] = step < min_length ? eos : -1;
+  c[VC_HIST + 1 + lane] = lane < n_bad ? bad.w[lane] : -1;
+  __syncthreads();
+  if (lane < VC_HIST) {
+    bool hit = ngram >= 1 && lane < step && lane >= ngram - 1 && step >= ngram - 1;
+    for (int k = 1; hit && k < ngram; ++k) hit = c[lane - k] == c[step - k] && c[lane - k] >= 0;   // (no word matches nothing)
+    f[lane] = hit ? 1 : 0;
+  }
+  __syncthreads();
+  if (!live) return;
+  for (int j = lane; j < nw; j += 64) {
+    unsigned ban = 0u, seen = 0u;
+    for (int e = 0; e < step; ++e) {                       // (step <= VC_HIST)
+      const int wd = c[e];
+      if (wd >= 0 && (wd >> 5) == j) seen |= 1u << (wd & 31), ban |= f[e] ? 1u << (wd & 31) : 0u;
+    }
+    for (int e = VC_HIST; e < VC_HIST + 1 + n_bad; ++e) {
+      const int wd = c[e];
+      if (wd >= 0 && wd < V && (wd >> 5) == j) ban |= 1u << (wd & 31);
+    }
+    bits[((size_t)row * 2) * nw + j] = ban;
+    bits[((size_t)row * 2 + 1) * nw + j] = seen;
+  }
+}
+
+// The bits of a chunk of 64 words for the workgroup's 16 rows: 2 planes x 16 rows x 2 words, fetched by the first wave one
+// chunk ahead (beside the weight staging) and handed over through LDS between the two barriers of the staging: one load
+// per chunk and thread instead of one per compare.  Declares s_cb, cbit and the lambda fetch_bits(v0); reads tid, bits, nw,
+// row0, R.  v0 is a multiple of 64 below V, so both words exist (nw = 2 ceil(V / 64)).
+#define SPACAP_VC_BITS()                                                                                        \
+  __shared__ unsigned s_cb[2][VA_ROWS][2];                                                                      \
+  unsigned cbit = 0u;                                                                                           \
+  auto fetch_bits = [&](int v0) {                                                                               \
+    if (tid < 64) cbit = bits[((size_t)min(row0 + ((tid >> 1) & 15), R - 1) * 2 + (tid >> 5)) * nw + (v0 >> 5) + (tid & 1)]; \
+  }
+#define SPACAP_VC_STORE_BITS() \
+  if (tid < 64) s_cb[tid >> 5][(tid >> 1) & 15][tid & 1] = cbit
+// The lane's word is word 16 w + l15 of the chunk: bit 16 (w & 1) + l15 of word w >> 1.  Declares cban (banned) and applies
+// the penalty to `val` (one fp32 operation) for row 4 lg + u; reads theta.
+#define SPACAP_VC_APPLY(val, u)                                                              \
+  const unsigned cbm = 1u << (16 * (w & 1) + l15);                                           \
+  const unsigned cban = s_cb[0][4 * lg + (u)][w >> 1] & cbm;                                 \
+  if (s_cb[1][4 * lg + (u)][w >> 1] & cbm) val = val > 0.f ? val / theta : val * theta
+
+// vocab_argmax_kernel over z': a banned word never becomes a lane's best; a slice without an allowed word hands (-inf, v_beg)
+// to decode_next_kernel, where every finite winner is ahead of it.
+__global__ __launch_bounds__(256) void vocab_argmax_constrained_kernel(const float *__restrict__ x, const __bf16 *__restrict__ Wp,
+                                                                       const float *__restrict__ bias, long R, int V, int per_slice,
+                                                                       const unsigned *__restrict__ bits, int nw, float theta,
+                                                                       float *__restrict__ best_v, int *__restrict__ best_i) {
+  __shared__ __attribute__((aligned(16))) __bf16 s_w[VA_STAGE_ELEMS];
+  __shared__ float s_bv[4][VA_ROWS][17];
+  __shared__ int s_bi[4][VA_ROWS][17];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
+  const long row0 = (long)blockIdx.x * VA_ROWS;
+  const int ns = gridDim.y, sl = blockIdx.y;
+  const int v_beg = sl * per_slice, v_end = min(V, v_beg + per_slice);
+  SPACAP_VA_SPLIT_ROWS();   // bf16x8 a[kc][piece]
+  float bv[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  int bi[4] = {v_beg, v_beg, v_beg, v_beg};
+  SPACAP_VC_BITS();         // s_cb, cbit, fetch_bits(v0)
+  SPACAP_VA_STAGING();      // stg, fetch(v0)
+  fetch(v_beg < V ? v_beg : 0);
+  fetch_bits(v_beg < V ? v_beg : 0);
+  for (int v0 = v_beg; v0 < v_end; v0 += VA_CHUNK) {
+    __syncthreads();
+    SPACAP_VA_STORE_STAGE();
+    SPACAP_VC_STORE_BITS();
+    __syncthreads();
+    if (v0 + VA_CHUNK < v_end) fetch(v0 + VA_CHUNK), fetch_bits(v0 + VA_CHUNK);
+    const int v = v0 + 16 * w + l15;                    // this lane's word of the chunk
+    SPACAP_VA_TILE();                                   // acc, acc2
+    if (v < v_end) {
+      const float bsv = bias[v];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float val = (acc[u] + acc2[u]) + bsv;           // (the greedy kernel's logit, bit for bit)
+        SPACAP_VC_APPLY(val, u);
+        if (!cban && val > bv[u]) bv[u] = val, bi[u] = v;
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) s_bv[w][4 * lg + u][l15] = bv[u], s_bi[w][4 * lg + u][l15] = bi[u];
+  __syncthreads();
+  if (tid < 64) {
+    const int row = tid >> 2, ww = tid & 3;          // four threads per sequence, one wave's 16 candidates each
+    float m = -INFINITY;
+    int mi = 0x7fffffff;
+#pragma unroll
+    for (int l = 0; l < 16; ++l) {
+      const float val = s_bv[ww][row][l];
+      const int idx = s_bi[ww][row][l];
+      if (SPACAP_FIRST_MAX(val, idx, m, mi)) m = val, mi = idx;
+    }
+#pragma unroll
+    for (int o = 1; o <= 2; o <<= 1) {
+      const float om = __shfl_xor(m, o);
+      const int oi = __shfl_xor(mi, o);
+      if (SPACAP_FIRST_MAX(om, oi, m, mi)) m = om, mi = oi;
+    }
+    if (ww == 0 && row0 + row < R) {
+      best_v[(size_t)(row0 + row) * ns + sl] = m;
+      best_i[(size_t)(row0 + row) * ns + sl] = mi;
+    }
+  }
+}
+
+// beam_topw_kernel over z': a banned word adds no term to the row's (max, sum exp) -- exp(-inf) = 0 -- and enters no list, so
+// the merge kernel's log-probabilities are log_softmax(z').  A row with fewer than W allowed words ends its list with
+// (-inf, NO_WORD) entries.
+template <int WB>
+__global__ __launch_bounds__(256) void beam_topw_constrained_kernel(const float *__restrict__ x, const __bf16 *__restrict__ Wp,
+                                                                    const float *__restrict__ bias, long R, int V, int per_slice,
+                                                                    const unsigned *__restrict__ bits, int nw, float theta, int W,
+                                                                    float *__restrict__ part_v, int *__restrict__ part_i,
+                                                                    float *__restrict__ part_ms) {
+  __shared__ __attribute__((aligned(16))) __bf16 s_w[VA_STAGE_ELEMS];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
+  const long row0 = (long)blockIdx.x * VA_ROWS;
+  const int ns = gridDim.y, sl = blockIdx.y;
+  const int v_beg = sl * per_slice, v_end = min(V, v_beg + per_slice);
+  SPACAP_VA_SPLIT_ROWS();   // bf16x8 a[kc][piece]
+  float tv[4][WB], mx[4], sm[4];
+  int ti[4][WB];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    mx[u] = -INFINITY, sm[u] = 0.f;
+#pragma unroll
+    for (int k = 0; k < WB; ++k) tv[u][k] = -INFINITY, ti[u][k] = NO_WORD;
+  }
+  SPACAP_VC_BITS();         // s_cb, cbit, fetch_bits(v0)
+  SPACAP_VA_STAGING();      // stg, fetch(v0)
+  fetch(v_beg < V ? v_beg : 0);
+  fetch_bits(v_beg < V ? v_beg : 0);
+  for (int v0 = v_beg; v0 < v_end; v0 += VA_CHUNK) {
+    __syncthreads();
+    SPACAP_VA_STORE_STAGE();
+    SPACAP_VC_STORE_BITS();
+    __syncthreads();
+    if (v0 + VA_CHUNK < v_end) fetch(v0 + VA_CHUNK), fetch_bits(v0 + VA_CHUNK);
+    const int v = v0 + 16 * w + l15;                    // this lane's word of the chunk
+    SPACAP_VA_TILE();                                   // acc, acc2
+    if (v < v_end) {
+      const float bsv = bias[v];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float val = (acc[u] + acc2[u]) + bsv;           // (the greedy kernel's logit, bit for bit)
+        SPACAP_VC_APPLY(val, u);
+        if (!cban) {
+          if (val > mx[u]) sm[u] = sm[u] * expf(mx[u] - val) + 1.f, mx[u] = val;
+          else sm[u] += expf(val - mx[u]);
+          if (val > tv[u][WB - 1]) {
+            float cv = val;
+            int ci = v;
+#pragma unroll
+            for (int k = 0; k < WB; ++k)
+              if (SPACAP_FIRST_MAX(cv, ci, tv[u][k], ti[u][k])) {
+                const float ov = tv[u][k];
+                const int oi = ti[u][k];
+                tv[u][k] = cv, ti[u][k] = ci, cv = ov, ci = oi;
+              }
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();   // every wave is done with the last chunk: the staging buffer becomes the merge area
+  float *s_mv = reinterpret_cast<float *>(s_w);               // [4 waves][16 rows][WB]
+  int *s_mi = reinterpret_cast<int *>(s_mv + 4 * VA_ROWS * WB);
+  float *s_ms = reinterpret_cast<float *>(s_mi + 4 * VA_ROWS * WB);   // [4][16][2]
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int row = 4 * lg + u;
+    float M = mx[u];
+#pragma unroll
+    for (int o = 1; o <= 8; o <<= 1) M = fmaxf(M, __shfl_xor(M, o));
+    float S = mx[u] == -INFINITY ? 0.f : sm[u] * expf(mx[u] - M);
+#pragma unroll
+    for (int o = 1; o <= 8; o <<= 1) S += __shfl_xor(S, o);
+    if (l15 == 0) s_ms[(w * VA_ROWS + row) * 2] = M, s_ms[(w * VA_ROWS + row) * 2 + 1] = S;
+#pragma unroll
+    for (int k = 0; k < WB; ++k) {
+      if (k >= W) break;
+      float bvv = tv[u][0];
+      int bii = ti[u][0];
+#pragma unroll
+      for (int o = 1; o <= 8; o <<= 1) {
+        const float ov = __shfl_xor(bvv, o);
+        const int oi = __shfl_xor(bii, o);
+        if (SPACAP_FIRST_MAX(ov, oi, bvv, bii)) bvv = ov, bii = oi;
+      }
+      if (ti[u][0] == bii) {   // (a word sits in one lane only; empty heads all pop, which changes nothing)
+#pragma unroll
+        for (int q = 0; q + 1 < WB; ++q) tv[u][q] = tv[u][q + 1], ti[u][q] = ti[u][q + 1];
+        tv[u][WB - 1] = -INFINITY, ti[u][WB - 1] = NO_WORD;
+      }
+      if (l15 == 0) s_mv[(w * VA_ROWS + row) * WB + k] = bvv, s_mi[(w * VA_ROWS + row) * WB + k] = bii;
+    }
+  }
+  __syncthreads();
+  if (tid < VA_ROWS && row0 + tid < R) {   // one thread per sequence: the four waves' sorted lists, merged
+    const int row = tid;
+    const size_t o = ((size_t)(row0 + row) * ns + sl);
+    int hd[4] = {0, 0, 0, 0};
+    for (int k = 0; k < W; ++k) {
+      float bvv = -INFINITY;
+      int bii = NO_WORD, bw = 0;
+#pragma unroll
+      for (int ww = 0; ww < 4; ++ww) {
+        const bool has = hd[ww] < W;
+        const float cv = has ? s_mv[(ww * VA_ROWS + row) * WB + hd[ww]] : -INFINITY;
+        const int ci = has ? s_mi[(ww * VA_ROWS + row) * WB + hd[ww]] : NO_WORD;
+        if (SPACAP_FIRST_MAX(cv, ci, bvv, bii)) bvv = cv, bii = ci, bw = ww;
+      }
+#pragma unroll
+      for (int ww = 0; ww < 4; ++ww) hd[ww] += ww == bw ? 1 : 0;
+      part_v[o * W + k] = bvv, part_i[o * W + k] = bii;
+    }
+    float M = -INFINITY, S = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww) M = fmaxf(M, s_ms[(ww * VA_ROWS + row) * 2]);
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww) {
+      const float m = s_ms[(ww * VA_ROWS + row) * 2];
+      S += m == -INFINITY ? 0.f : s_ms[(ww * VA_ROWS + row) * 2 + 1] * expf(m - M);
+    }
+    part_ms[o * 2] = M, part_ms[o * 2 + 1] = S;
+  }
+}
+
+// vocab_gumbel_kernel over z': z_v = z'_v / tau + g_v; a banned word is never drawn and adds nothing to (max, sum exp), so
+// sample_next_kernel's log-probability is log_softmax(z')[word].
+__global__ __launch_bounds__(256) void vocab_gumbel_constrained_kernel(const float *__restrict__ x, const __bf16 *__restrict__ Wp,
+                                                                       const float *__restrict__ bias, long R, int V, int per_slice,
+                                                                       const unsigned *__restrict__ bits, int nw, float theta, float inv_tau,
+                                                                       unsigned long long seed, const unsigned long long *__restrict__ seed_dev,
+                                                                       int n_words, int step, float *__restrict__ part_z,
+                                                                       int *__restrict__ part_w, float *__restrict__ part_l,
+                                                                       float *__restrict__ part_ms) {
+  __shared__ __attribute__((aligned(16))) __bf16 s_w[VA_STAGE_ELEMS];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
+  const long row0 = (long)blockIdx.x * VA_ROWS;
+  const int ns = gridDim.y, sl = blockIdx.y;
+  const int v_beg = sl * per_slice, v_end = min(V, v_beg + per_slice);
+  const DropSeed sd = make_seed(seed, seed_dev);
+  SPACAP_VA_SPLIT_ROWS();   // bf16x8 a[kc][piece]
+  float bz[4], bl[4], mx[4], sm[4];
+  int bi[4];
+  unsigned long long nbase[4];   // the noise index of word 0 of row row0 + 4 lg + u at this step
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    bz[u] = -INFINITY, bl[u] = -INFINITY, bi[u] = NO_WORD, mx[u] = -INFINITY, sm[u] = 0.f;
+    nbase[u] = ((unsigned long long)(row0 + 4 * lg + u) * (unsigned long long)n_words + (unsigned long long)step) * (unsigned long long)V;
+  }
+  SPACAP_VC_BITS();         // s_cb, cbit, fetch_bits(v0)
+  SPACAP_VA_STAGING();      // stg, fetch(v0)
+  fetch(v_beg < V ? v_beg : 0);
+  fetch_bits(v_beg < V ? v_beg : 0);
+  for (int v0 = v_beg; v0 < v_end; v0 += VA_CHUNK) {
+    __syncthreads();
+    SPACAP_VA_STORE_STAGE();
+    SPACAP_VC_STORE_BITS();
+    __syncthreads();
+    if (v0 + VA_CHUNK < v_end) fetch(v0 + VA_CHUNK), fetch_bits(v0 + VA_CHUNK);
+    const int v = v0 + 16 * w + l15;                    // this lane's word of the chunk
+    SPACAP_VA_TILE();                                   // acc, acc2
+    if (v < v_end) {
+      const float bsv = bias[v];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float val = (acc[u] + acc2[u]) + bsv;           // (the greedy kernel's logit, bit for bit)
+        SPACAP_VC_APPLY(val, u);
+        if (!cban) {
+          if (val > mx[u]) sm[u] = sm[u] * expf(mx[u] - val) + 1.f, mx[u] = val;
+          else sm[u] += expf(val - mx[u]);
+          const float z = val * inv_tau + gumbel_noise(nbase[u] + (unsigned long long)v, sd);
+          if (z > bz[u]) bz[u] = z, bi[u] = v, bl[u] = val;
+        }
+      }
+    }
+  }
+  __syncthreads();   // every wave is done with the last chunk: the staging buffer becomes the merge area
+  constexpr int MA = 4 * VA_ROWS * 17;                        // [4 waves][16 rows][16 lanes + 1]
+  float *s_z = reinterpret_cast<float *>(s_w);
+  int *s_i = reinterpret_cast<int *>(s_z + MA);
+  float *s_l = reinterpret_cast<float *>(s_i + MA), *s_m = s_l + MA, *s_s = s_m + MA;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int o = (w * VA_ROWS + 4 * lg + u) * 17 + l15;
+    s_z[o] = bz[u], s_i[o] = bi[u], s_l[o] = bl[u], s_m[o] = mx[u], s_s[o] = sm[u];
+  }
+  __syncthreads();
+  if (tid < 64) {
+    const int row = tid >> 2, ww = tid & 3;          // four threads per sequence, one wave's 16 lanes each
+    const int o = (ww * VA_ROWS + row) * 17;
+    float m = -INFINITY, ml = -INFINITY, M = -INFINITY, S = 0.f;
+    int mi = NO_WORD;
+#pragma unroll
+    for (int l = 0; l < 16; ++l) {
+      const float val = s_z[o + l];
+      const int idx = s_i[o + l];
+      if (SPACAP_FIRST_MAX(val, idx, m, mi)) m = val, mi = idx, ml = s_l[o + l];
+      M = fmaxf(M, s_m[o + l]);
+    }
+#pragma unroll
+    for (int l = 0; l < 16; ++l) {
+      const float lm = s_m[o + l];
+      S += lm == -INFINITY ? 0.f : s_s[o + l] * expf(lm - M);
+    }
+#pragma unroll
+    for (int q = 1; q <= 2; q <<= 1) {
+      const float om = __shfl_xor(m, q), ol = __shfl_xor(ml, q), oM = __shfl_xor(M, q), oS = __shfl_xor(S, q);
+      const int oi = __shfl_xor(mi, q);
+      if (SPACAP_FIRST_MAX(om, oi, m, mi)) m = om, mi = oi, ml = ol;
+      const float nM = fmaxf(M, oM);
+      S = (M == -INFINITY ? 0.f : S * expf(M - nM)) + (oM == -INFINITY ? 0.f : oS * expf(oM - nM));
+      M = nM;
+    }
+    if (ww == 0 && row0 + row < R) {
+      const size_t e = (size_t)(row0 + row) * ns + sl;
+      part_z[e] = m, part_w[e] = mi, part_l[e] = ml, part_ms[2 * e] = M, part_ms[2 * e + 1] = S;
+    }
+  }
+}
+
+// Nucleus sampling keeps the step's logits in HBM between its two launches anyway: z' is made by patching the image.  One
+// thread per (row, image word): the set bits of "seen" and "banned" name the <= ~100 logits of the row that change.
+__global__ __launch_bounds__(256) void logits_constrain_kernel(float *__restrict__ img, int ld, const unsigned *__restrict__ bits, int nw,
+                                                               long rows, int V, float theta) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * nw) return;
+  const long r = idx / nw;
+  const int j = (int)(idx - r * nw);
+  const unsigned ban = bits[((size_t)r * 2) * nw + j], seen = bits[((size_t)r * 2 + 1) * nw + j];
+  for (unsigned any = ban | seen; any; any &= any - 1) {
+    const int b = __ffs((int)any) - 1, v = 32 * j + b;
+    if (v >= V) break;
+    float *p = img + (size_t)r * ld + v;
+    float val = *p;
+    if ((seen >> b) & 1u) val = val > 0.f ? val / theta : val * theta;
+    if ((ban >> b) & 1u) val = -INFINITY;
+    *p = val;
+  }
+}
+
+// the arguments every constrained word choice shares: the images of decode_constraint_kernel and the penalty
+inline bool vc_ok(const void *bits, float theta) { return bits != nullptr && isfinite(theta) && theta >= 1.f; }
+
 }  // namespace
 
 extern "C" int spacap_decode_attn_f32(const float *qkv, float *kcache, float *vcache, long R, int h, int d_k, int T, int t, float scale,
@@ -890,9 +1294,9 @@ extern "C" size_t spacap_beam_topw_workspace_bytes(long rows, int V, int W) {
   return rows > 0 && V > 0 && W >= 1 && W <= BEAM_MAX ? (size_t)rows * va_slices(rows, V) * (8 * (size_t)W + 8) : 0;
 }
 
-extern "C" int spacap_beam_topw_f32(const float *x, const void *Wp, const float *bias, long rows, int V, int W, float *top_logp,
-                                    int32_t *top_word, void *workspace, spacap_stream_t stream) {
-  const char *what = "spacap_beam_topw_f32";
+// bits == nullptr: the unconstrained kernels, as ever; else the constrained ones over the images `bits` with penalty theta
+static int beam_topw_impl(const char *what, const float *x, const void *Wp, const float *bias, long rows, int V, int W, const uint32_t *bits,
+                          float theta, float *top_logp, int32_t *top_word, void *workspace, spacap_stream_t stream) {
   SPACAP_REQUIRE(rows >= 0 && V >= 1 && W >= 1 && W <= BEAM_MAX && W <= V, "%s: (rows=%ld, V=%d, W=%d) unsupported: 1 <= W <= %d and W <= V",
                  what, rows, V, W, BEAM_MAX);
   if (rows == 0) return SPACAP_OK;
@@ -906,12 +1310,31 @@ extern "C" int spacap_beam_topw_f32(const float *x, const void *Wp, const float 
   hipStream_t s = spacap::as_stream(stream);
   const dim3 grid((unsigned)((rows + VA_ROWS - 1) / VA_ROWS), ns);
   const __bf16 *wp = static_cast<const __bf16 *>(Wp);
-  if (W <= 4) hipLaunchKernelGGL((beam_topw_kernel<4>), grid, dim3(256), 0, s, x, wp, bias, rows, V, per, W, pv, pi, pms);
-  else hipLaunchKernelGGL((beam_topw_kernel<8>), grid, dim3(256), 0, s, x, wp, bias, rows, V, per, W, pv, pi, pms);
+  const int nw = vc_words(V);
+  if (bits == nullptr) {
+    if (W <= 4) hipLaunchKernelGGL((beam_topw_kernel<4>), grid, dim3(256), 0, s, x, wp, bias, rows, V, per, W, pv, pi, pms);
+    else hipLaunchKernelGGL((beam_topw_kernel<8>), grid, dim3(256), 0, s, x, wp, bias, rows, V, per, W, pv, pi, pms);
+  } else if (W <= 4) {
+    hipLaunchKernelGGL((beam_topw_constrained_kernel<4>), grid, dim3(256), 0, s, x, wp, bias, rows, V, per, bits, nw, theta, W, pv, pi, pms);
+  } else {
+    hipLaunchKernelGGL((beam_topw_constrained_kernel<8>), grid, dim3(256), 0, s, x, wp, bias, rows, V, per, bits, nw, theta, W, pv, pi, pms);
+  }
   hipLaunchKernelGGL(beam_topw_merge_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, pv, pi, pms, ns, rows, W, top_logp,
                      reinterpret_cast<int *>(top_word));
   SPACAP_CHECK_LAUNCH(what);
   return SPACAP_OK;
+}
+
+extern "C" int spacap_beam_topw_f32(const float *x, const void *Wp, const float *bias, long rows, int V, int W, float *top_logp,
+                                    int32_t *top_word, void *workspace, spacap_stream_t stream) {
+  return beam_topw_impl("spacap_beam_topw_f32", x, Wp, bias, rows, V, W, nullptr, 1.f, top_logp, top_word, workspace, stream);
+}
+
+extern "C" int spacap_beam_topw_constrained_f32(const float *x, const void *Wp, const float *bias, long rows, int V, int W, const uint32_t *bits,
+                                                float theta, float *top_logp, int32_t *top_word, void *workspace, spacap_stream_t stream) {
+  const char *what = "spacap_beam_topw_constrained_f32";
+  SPACAP_REQUIRE(vc_ok(bits, theta), "%s: bits must not be null and the repetition penalty %g must be finite and >= 1", what, (double)theta);
+  return beam_topw_impl(what, x, Wp, bias, rows, V, W, bits, theta, top_logp, top_word, workspace, stream);
 }
 
 extern "C" int spacap_decode_attn_beam_f32(const float *qkv, float *kcache, float *vcache, const int8_t *anc, long R, int W, int h, int d_k,
@@ -978,11 +1401,10 @@ extern "C" size_t spacap_sample_word_workspace_bytes(long rows, int V, int top_k
   return spacap_beam_topw_workspace_bytes(rows, V, top_k) + (size_t)rows * top_k * 8;
 }
 
-extern "C" int spacap_sample_word_f32(const float *x, const void *Wp, const float *bias, long rows, int V, int top_k, float inv_tau,
-                                      uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos, const float *lut, float scale,
-                                      const float *pe_row, int64_t *ys, float *score, int32_t *length, int32_t *finished, float *xw,
-                                      void *workspace, spacap_stream_t stream) {
-  const char *what = "spacap_sample_word_f32";
+static int sample_word_impl(const char *what, const float *x, const void *Wp, const float *bias, long rows, int V, int top_k, float inv_tau,
+                            uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos, const uint32_t *bits, float theta,
+                            const float *lut, float scale, const float *pe_row, int64_t *ys, float *score, int32_t *length,
+                            int32_t *finished, float *xw, void *workspace, spacap_stream_t stream) {
   SPACAP_REQUIRE(rows >= 0 && V >= 1, "%s: (rows=%ld, V=%d) unsupported: rows >= 0 and V >= 1", what, rows, V);
   SPACAP_REQUIRE(top_k >= 0 && top_k <= BEAM_MAX && top_k <= V, "%s: top_k=%d unsupported: 0 <= top_k <= min(%d, V=%d)", what, top_k,
                  BEAM_MAX, V);
@@ -1004,15 +1426,22 @@ extern "C" int spacap_sample_word_f32(const float *x, const void *Wp, const floa
     float *wz = static_cast<float *>(workspace);
     int *ww = reinterpret_cast<int *>(wz + (size_t)rows * ns);
     float *wl = reinterpret_cast<float *>(ww + (size_t)rows * ns), *wms = wl + (size_t)rows * ns;
-    hipLaunchKernelGGL(vocab_gumbel_kernel, dim3((unsigned)((rows + VA_ROWS - 1) / VA_ROWS), ns), dim3(256), 0, s, x,
-                       static_cast<const __bf16 *>(Wp), bias, rows, V, per, inv_tau, (unsigned long long)seed, sdev, n_words, step, wz, ww, wl,
-                       wms);
+    if (bits == nullptr)
+      hipLaunchKernelGGL(vocab_gumbel_kernel, dim3((unsigned)((rows + VA_ROWS - 1) / VA_ROWS), ns), dim3(256), 0, s, x,
+                         static_cast<const __bf16 *>(Wp), bias, rows, V, per, inv_tau, (unsigned long long)seed, sdev, n_words, step, wz, ww, wl,
+                         wms);
+    else
+      hipLaunchKernelGGL(vocab_gumbel_constrained_kernel, dim3((unsigned)((rows + VA_ROWS - 1) / VA_ROWS), ns), dim3(256), 0, s, x,
+                         static_cast<const __bf16 *>(Wp), bias, rows, V, per, bits, vc_words(V), theta, inv_tau, (unsigned long long)seed, sdev,
+                         n_words, step, wz, ww, wl, wms);
     pz = wz, pw = ww, pl = wl, pms = wms;
   } else {
     char *base = static_cast<char *>(workspace);
     float *lp = reinterpret_cast<float *>(base + spacap_beam_topw_workspace_bytes(rows, V, top_k));
     int32_t *wd = reinterpret_cast<int32_t *>(lp + (size_t)rows * top_k);
-    const int rc = spacap_beam_topw_f32(x, Wp, bias, rows, V, top_k, lp, wd, workspace, stream);
+    // (unconstrained: the top-W entry reports its refusals under its own name, as it always did)
+    const int rc = beam_topw_impl(bits == nullptr ? "spacap_beam_topw_f32" : what, x, Wp, bias, rows, V, top_k, bits, theta, lp, wd, workspace,
+                                  stream);
     if (rc != SPACAP_OK) return rc;
     top_lp = lp, top_wd = reinterpret_cast<const int *>(wd);
   }
@@ -1021,6 +1450,24 @@ extern "C" int spacap_sample_word_f32(const float *x, const void *Wp, const floa
                      reinterpret_cast<int *>(length), reinterpret_cast<int *>(finished), xw);
   SPACAP_CHECK_LAUNCH(what);
   return SPACAP_OK;
+}
+
+extern "C" int spacap_sample_word_f32(const float *x, const void *Wp, const float *bias, long rows, int V, int top_k, float inv_tau,
+                                      uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos, const float *lut, float scale,
+                                      const float *pe_row, int64_t *ys, float *score, int32_t *length, int32_t *finished, float *xw,
+                                      void *workspace, spacap_stream_t stream) {
+  return sample_word_impl("spacap_sample_word_f32", x, Wp, bias, rows, V, top_k, inv_tau, seed, seed_dev, n_words, step, eos, nullptr, 1.f, lut,
+                          scale, pe_row, ys, score, length, finished, xw, workspace, stream);
+}
+
+extern "C" int spacap_sample_word_constrained_f32(const float *x, const void *Wp, const float *bias, long rows, int V, int top_k, float inv_tau,
+                                                  uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos, const uint32_t *bits,
+                                                  float theta, const float *lut, float scale, const float *pe_row, int64_t *ys, float *score,
+                                                  int32_t *length, int32_t *finished, float *xw, void *workspace, spacap_stream_t stream) {
+  const char *what = "spacap_sample_word_constrained_f32";
+  SPACAP_REQUIRE(vc_ok(bits, theta), "%s: bits must not be null and the repetition penalty %g must be finite and >= 1", what, (double)theta);
+  return sample_word_impl(what, x, Wp, bias, rows, V, top_k, inv_tau, seed, seed_dev, n_words, step, eos, bits, theta, lut, scale, pe_row, ys,
+                          score, length, finished, xw, workspace, stream);
 }
 
 /* Nucleus (top-p) sampling ("Top-p"): spacap_sample_word_f32's step with the draw restricted to the
@@ -1032,11 +1479,10 @@ extern "C" size_t spacap_sample_word_nucleus_workspace_bytes(long rows, int V) {
   return rows > 0 && V >= 1 && V <= NUC_MAX_V ? (size_t)rows * nuc_ld(V) * sizeof(float) : 0;
 }
 
-extern "C" int spacap_sample_word_nucleus_f32(const float *x, const void *Wp, const float *bias, long rows, int V, float top_p, float inv_tau,
-                                              uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos, const float *lut,
-                                              float scale, const float *pe_row, int64_t *ys, float *score, int32_t *length,
-                                              int32_t *finished, float *xw, void *workspace, spacap_stream_t stream) {
-  const char *what = "spacap_sample_word_nucleus_f32";
+static int sample_word_nucleus_impl(const char *what, const float *x, const void *Wp, const float *bias, long rows, int V, float top_p,
+                                    float inv_tau, uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos,
+                                    const uint32_t *bits, float theta, const float *lut, float scale, const float *pe_row, int64_t *ys,
+                                    float *score, int32_t *length, int32_t *finished, float *xw, void *workspace, spacap_stream_t stream) {
   SPACAP_REQUIRE(rows >= 0 && V >= 1 && V <= NUC_MAX_V, "%s: (rows=%ld, V=%d) unsupported: rows >= 0 and 1 <= V <= %d", what, rows, V,
                  NUC_MAX_V);
   SPACAP_REQUIRE(isfinite(top_p) && top_p > 0.f && top_p <= 1.f, "%s: top_p = %g must lie in (0, 1]", what, (double)top_p);
@@ -1054,9 +1500,90 @@ extern "C" int spacap_sample_word_nucleus_f32(const float *x, const void *Wp, co
   SPACAP_CHECK_HIP(spacap::allow_dynamic_lds(reinterpret_cast<const void *>(&nucleus_next_kernel), NUC_MAX_V * 8, lds_ok), what);
   hipLaunchKernelGGL(vocab_logits_kernel, dim3((unsigned)((rows + VA_ROWS - 1) / VA_ROWS), ns), dim3(256), 0, s, x,
                      static_cast<const __bf16 *>(Wp), bias, rows, V, per, ld, img);
+  if (bits != nullptr) {   // z' in place: the image is this mode's own copy of the logits
+    const int nw = vc_words(V);
+    hipLaunchKernelGGL(logits_constrain_kernel, dim3((unsigned)((rows * nw + 255) / 256)), dim3(256), 0, s, img, ld, bits, nw, rows, V, theta);
+  }
   hipLaunchKernelGGL(nucleus_next_kernel, dim3((unsigned)rows), dim3(256), (size_t)V * 8, s, img, ld, top_p, inv_tau,
                      (unsigned long long)seed, reinterpret_cast<const unsigned long long *>(seed_dev), V, n_words, step, eos, lut, scale,
                      pe_row, reinterpret_cast<long long *>(ys), score, reinterpret_cast<int *>(length), reinterpret_cast<int *>(finished), xw);
+  SPACAP_CHECK_LAUNCH(what);
+  return SPACAP_OK;
+}
+
+extern "C" int spacap_sample_word_nucleus_f32(const float *x, const void *Wp, const float *bias, long rows, int V, float top_p, float inv_tau,
+                                              uint64_t seed, const uint64_t *seed_dev, int n_words, int step, int eos, const float *lut,
+                                              float scale, const float *pe_row, int64_t *ys, float *score, int32_t *length,
+                                              int32_t *finished, float *xw, void *workspace, spacap_stream_t stream) {
+  return sample_word_nucleus_impl("spacap_sample_word_nucleus_f32", x, Wp, bias, rows, V, top_p, inv_tau, seed, seed_dev, n_words, step, eos,
+                                  nullptr, 1.f, lut, scale, pe_row, ys, score, length, finished, xw, workspace, stream);
+}
+
+extern "C" int spacap_sample_word_nucleus_constrained_f32(const float *x, const void *Wp, const float *bias, long rows, int V, float top_p,
+                                                          float inv_tau, uint64_t seed, const uint64_t *seed_dev, int n_words, int step,
+                                                          int eos, const uint32_t *bits, float theta, const float *lut, float scale,
+                                                          const float *pe_row, int64_t *ys, float *score, int32_t *length, int32_t *finished,
+                                                          float *xw, void *workspace, spacap_stream_t stream) {
+  const char *what = "spacap_sample_word_nucleus_constrained_f32";
+  SPACAP_REQUIRE(vc_ok(bits, theta), "%s: bits must not be null and the repetition penalty %g must be finite and >= 1", what, (double)theta);
+  return sample_word_nucleus_impl(what, x, Wp, bias, rows, V, top_p, inv_tau, seed, seed_dev, n_words, step, eos, bits, theta, lut, scale,
+                                  pe_row, ys, score, length, finished, xw, workspace, stream);
+}
+
+/* Constrained decoding: the two bit images of every row for step `step` -- bits u32 [rows][2][nw],
+   nw = 2 ceil(V / 64): plane 0 the banned words (bad_words, eos while step < min_length, the no-repeat n-gram rule), plane 1
+   the words of the row's history.  rows = R W.  The history is either ys i64 [rows][ys_ld] columns 0 .. step - 1 (greedy and
+   sampled decoding, W = 1) or, with ys null, a beam's: trace_word i32 [n_words][R][W] read through anc i8 [R W][T], the
+   ancestor table of position step + 1 (spacap_beam_step_f32).  bad_words i32 [n_bad] in HOST memory, n_bad <= 64, read during the call. */
+extern "C" size_t spacap_decode_constraints_bytes(long rows, int V) { return rows > 0 && V >= 1 ? (size_t)rows * 2 * vc_words(V) * 4 : 0; }
+
+extern "C" int spacap_decode_constraints(const int64_t *ys, int ys_ld, const int32_t *trace_word, const int8_t *anc, long R, int W, int T, int V,
+                                         int step, int eos, int min_length, int no_repeat_ngram, const int32_t *bad_words, int n_bad,
+                                         uint32_t *bits, spacap_stream_t stream) {
+  const char *what = "spacap_decode_constraints";
+  SPACAP_REQUIRE(R >= 0 && W >= 1 && W <= BEAM_MAX && V >= 1 && T >= 2 && T <= 32, "%s: (R=%ld, W=%d, V=%d, T=%d) unsupported", what, R, W, V, T);
+  SPACAP_REQUIRE(step >= 0 && step <= VC_HIST && step + 1 < T, "%s: step=%d outside 0 .. T - 2 = %d", what, step, T - 2);
+  SPACAP_REQUIRE(eos >= 0 && eos < V && min_length >= 0 && no_repeat_ngram >= 0, "%s: (eos=%d, min_length=%d, no_repeat_ngram=%d) unsupported",
+                 what, eos, min_length, no_repeat_ngram);
+  SPACAP_REQUIRE(n_bad >= 0 && n_bad <= VC_MAX_BAD && (n_bad == 0 || bad_words), "%s: n_bad=%d outside 0..%d, or bad_words null", what, n_bad,
+                 VC_MAX_BAD);
+  SPACAP_REQUIRE((long)n_bad + step + 1 < V, "%s: %d bad words + %d history words + eos could leave no word of V=%d allowed", what, n_bad, step, V);
+  if (R == 0) return SPACAP_OK;
+  SPACAP_REQUIRE(bits != nullptr, "%s: null bits", what);
+  SPACAP_REQUIRE(ys != nullptr ? (W == 1 && ys_ld >= step && ys_ld >= 1) : (trace_word != nullptr && anc != nullptr),
+                 "%s: the history is ys (W = 1, ys_ld >= step) or trace_word with anc", what);
+  const long rows = R * W;
+  SPACAP_REQUIRE((rows + 3) / 4 <= 2147483647L, "%s: too many rows", what);
+  VcBad bad;
+  for (int i = 0; i < VC_MAX_BAD; ++i) bad.w[i] = i < n_bad ? bad_words[i] : -1;
+  hipLaunchKernelGGL(decode_constraint_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, spacap::as_stream(stream),
+                     reinterpret_cast<const long long *>(ys), ys_ld, reinterpret_cast<const int *>(trace_word),
+                     reinterpret_cast<const signed char *>(anc), R, W, T, rows, V, step, eos, min_length, no_repeat_ngram,
+                     bad, n_bad, reinterpret_cast<unsigned *>(bits), vc_words(V));
+  SPACAP_CHECK_LAUNCH(what);
+  return SPACAP_OK;
+}
+
+/* spacap_decode_word_f32 over the constrained logits: the same workspace, the same outputs. */
+extern "C" int spacap_decode_word_constrained_f32(const float *x, const void *W, const float *bias, long R, int V, const uint32_t *bits,
+                                                  float theta, const float *lut, float scale, const float *pe_row, int64_t *ys, int ys_ld,
+                                                  int t_out, float *x_next, void *workspace, spacap_stream_t stream) {
+  const char *what = "spacap_decode_word_constrained_f32";
+  SPACAP_REQUIRE(R >= 0 && V >= 1 && ys_ld >= 1 && t_out >= 0 && t_out < ys_ld, "%s: bad sizes", what);
+  SPACAP_REQUIRE(vc_ok(bits, theta), "%s: bits must not be null and the repetition penalty %g must be finite and >= 1", what, (double)theta);
+  if (R == 0) return SPACAP_OK;
+  SPACAP_REQUIRE(x && W && bias && lut && pe_row && ys && x_next && workspace && aligned16(x, W, lut, pe_row, x_next),
+                 "%s: null or unaligned pointer", what);
+  SPACAP_REQUIRE(R <= 16L * 2147483647L, "%s: too many sequences", what);
+  const int ns = va_slices(R, V);
+  const int per = va_per_slice(V, ns);
+  float *bv = static_cast<float *>(workspace);
+  int *bi = reinterpret_cast<int *>(bv + (size_t)R * ns);
+  hipStream_t s = spacap::as_stream(stream);
+  hipLaunchKernelGGL(vocab_argmax_constrained_kernel, dim3((unsigned)((R + VA_ROWS - 1) / VA_ROWS), ns), dim3(256), 0, s, x,
+                     static_cast<const __bf16 *>(W), bias, R, V, per, bits, vc_words(V), theta, bv, bi);
+  hipLaunchKernelGGL(decode_next_kernel, dim3((unsigned)((R + 7) / 8)), dim3(256), 0, s, bv, bi, ns, R, lut, scale, pe_row,
+                     reinterpret_cast<long long *>(ys), ys_ld, t_out, x_next);
   SPACAP_CHECK_LAUNCH(what);
   return SPACAP_OK;
 }

@@ -865,10 +865,13 @@ class Evaluator:
     (it runs once).  ``pred_*``, ``post_*`` and the caption metrics are those of ``"all"``; ``lang_cap`` holds the empty caption
     where nothing was decoded, and the forward also returns ``lang_cap_decoded`` and ``lang_cap_rows``.  ``decode_capacity``:
     None sizes the decoder's row list to the number of kept proposals (one 4-byte device-to-host read per call); an int in
-    1..B K fixes it (no host read; kept proposals beyond it, in (scene, proposal) order, are not decoded)."""
+    1..B K fixes it (no host read; kept proposals beyond it, in (scene, proposal) order, are not decoded).
+
+    ``constraints``: ``dict(min_length=, no_repeat_ngram=, repetition_penalty=, bad_words=)`` (every key optional): constrained
+    decoding in whichever mode is set -- sets the captioner's attributes of the same names."""
 
     def __init__(self, model, graph=True, postprocess=None, detection_ap=None, caption_eval=None, predictions=None, beam_size=None,
-                 length_penalty=None, sample=None, decode="all", decode_capacity=None):
+                 length_penalty=None, sample=None, decode="all", decode_capacity=None, constraints=None):
         self.model = model
         if decode not in ("all", "kept"):
             raise ValueError(f"Evaluator: decode {decode!r} must be 'all' or 'kept'")
@@ -903,6 +906,15 @@ class Evaluator:
             check_arguments("Evaluator: sample", S, tau, k, cap.model.generator.proj.out_features, top_p)
             cap.num_samples, cap.temperature, cap.top_k, cap.top_p = S, tau, k, top_p
             cap.sample_seed = None if sample.get("seed") is None else int(sample["seed"])
+        if constraints is not None:
+            if cap is None or not hasattr(cap, "no_repeat_ngram"):
+                raise ValueError("Evaluator: constraints need a model with a Transformer captioner")
+            from .decode_constraints import DecodeConstraints
+            from .transformer_captioner import MAX_DES_LEN
+            c = DecodeConstraints(**constraints)       # (unknown keys and bad values are refused here)
+            c.check("Evaluator: constraints", cap.model.generator.proj.out_features, MAX_DES_LEN + 1, cap.word_to_idx["eos"])
+            cap.min_length, cap.no_repeat_ngram, cap.repetition_penalty, cap.bad_words = (c.min_length, c.no_repeat_ngram,
+                                                                                          c.repetition_penalty, c.bad_words)
         self.post_kw = None
         for name, given in (("predictions", predictions), ("detection_ap", detection_ap), ("caption_eval", caption_eval)):
             if given is not None and postprocess is None:

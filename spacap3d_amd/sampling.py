@@ -98,13 +98,17 @@ def _first_max(z, words):
 
 
 @torch.no_grad()
-def sample(step_fn, R, S, n_words, sos, eos, temperature=1.0, top_k=0, seed=0, seed_dev=None, device=None, top_p=None):
+def sample(step_fn, R, S, n_words, sos, eos, temperature=1.0, top_k=0, seed=0, seed_dev=None, device=None, top_p=None, constraints=None):
     """``step_fn(i, words)`` returns the (R S, V) logits (before log-softmax) of word i of every row; ``words`` (R S,) int64
     are the newest words (``sos`` at i = 0).  Returns a dict: ``ys`` (R, S, n_words) int64, ``score`` (R, S) float32,
     ``length`` (R, S) int32 and ``gap`` (n_words, R S) float32: per row and step the best z minus the second-best one among
     the candidates (inf with one candidate; recorded for finished rows too).  ``top_p``: the nucleus restriction of the module's
-    docstring (None or 1.0: none)."""
+    docstring (None or 1.0: none).  ``constraints``: a ``decode_constraints.DecodeConstraints``: the
+    logits of every step are constrained over the row's own history before anything else sees them."""
+    from . import decode_constraints as dc
     from .beam_search import select_top
+    cons = dc.resolve(constraints)
+    hist = None
     R, S, n_words, sos, eos, k, tau = int(R), int(S), int(n_words), int(sos), int(eos), int(top_k), float(temperature)
     N = R * S
     words = torch.full((N,), sos, dtype=torch.long, device=device)
@@ -120,6 +124,11 @@ def sample(step_fn, R, S, n_words, sos, eos, temperature=1.0, top_k=0, seed=0, s
             length = torch.zeros(N, dtype=torch.int32, device=dev)
             lo, hi = seed_words(seed, seed_dev, dev)
             rho = torch.arange(N, dtype=torch.int64, device=dev)
+            if cons is not None:
+                cons.check("sample", V, n_words, eos)
+                hist = torch.zeros(N, n_words, dtype=torch.long, device=dev)
+        if cons is not None:
+            logits = dc.apply(cons, logits, hist, i, eos)
         logp = logits - torch.logsumexp(logits, 1, keepdim=True)
         base = ((rho * n_words + i) * V).unsqueeze(1)                  # the noise index of word 0 of every row at this step
         if k == 0:
@@ -139,6 +148,8 @@ def sample(step_fn, R, S, n_words, sos, eos, temperature=1.0, top_k=0, seed=0, s
         fin = fin | (word == eos)
         ys.append(word)
         gaps.append(gap)
+        if hist is not None:
+            hist[:, i] = word
         words = word
     return {"ys": torch.stack(ys, 1).view(R, S, n_words), "score": score.view(R, S), "length": length.view(R, S),
             "gap": torch.stack(gaps)}

@@ -832,10 +832,17 @@ class TransformerDecoderModel(nn.Module):
     sample_seed = None          # an integer: the same draws at every call (forward_eval's sample_seed, when that is None)
     last_sample_trace = None
 
+    # Constrained decoding, set the same way; every one is off at its default.
+    min_length = 0
+    no_repeat_ngram = 0
+    repetition_penalty = 1.0
+    bad_words = ()
+
     last_decode_slot = None     # forward_eval with a decode_mask: int32 (B K,), the packed row of every proposal (-1: not decoded)
 
     def forward_eval(self, ep, use_cache=True, beam_size=None, length_penalty=None, num_samples=None, temperature=None, top_k=None,
-                     sample_seed=None, top_p=None, decode_mask=None, decode_capacity=None):
+                     sample_seed=None, top_p=None, decode_mask=None, decode_capacity=None, min_length=None, no_repeat_ngram=None,
+                     repetition_penalty=None, bad_words=None):
         """Greedy decoding of B*K captions (:402-453).  The reference re-runs the 6-layer encoder AND the whole
         decoder prefix at each of the 31 steps; the encoder output does not depend on the words (computed once),
         and with ``use_cache`` the decoder keeps the keys / values of earlier positions so that each step only
@@ -877,7 +884,24 @@ class TransformerDecoderModel(nn.Module):
 
         With a mask ``use_cache=False`` raises ``ValueError``.  ``last_beam_trace`` / ``last_sample_trace`` keep the packed-row
         layout; ``last_decode_slot`` (and the traces' ``"slot"``) maps proposals to rows.  The sampler's noise is keyed by
-        ROW: a fixed ``sample_seed`` repeats the draws for a fixed mask, another mask gives other draws."""
+        ROW: a fixed ``sample_seed`` repeats the draws for a fixed mask, another mask gives other draws.
+
+        ``min_length``, ``no_repeat_ngram``, ``repetition_penalty``, ``bad_words`` (defaults: the module attributes, all off):
+        constrained decoding in every mode above (``decode_constraints.py``) -- no eos before
+        ``min_length`` words, no n-gram twice in a caption, the logits of used words divided (positive) or multiplied (else)
+        by the penalty, and a fixed set of words that are never chosen.  Log-probabilities and scores are those of the
+        constrained distribution.  With everything off the decoders run exactly the launches they run without the arguments;
+        with ``use_cache=False`` an active constraint raises ``ValueError``."""
+        from .decode_constraints import DecodeConstraints
+        cons = DecodeConstraints(self.min_length if min_length is None else min_length,
+                                 self.no_repeat_ngram if no_repeat_ngram is None else no_repeat_ngram,
+                                 self.repetition_penalty if repetition_penalty is None else repetition_penalty,
+                                 self.bad_words if bad_words is None else bad_words)
+        cons = cons if cons.active() else None
+        if cons is not None:
+            if not use_cache:
+                raise ValueError("forward_eval: constrained decoding keeps key / value caches (use_cache=False is the greedy parity path)")
+            cons.check("forward_eval", self.model.generator.proj.out_features, MAX_DES_LEN + 1, self.word_to_idx["eos"])
         W = int(self.beam_size if beam_size is None else beam_size)
         alpha = float(self.length_penalty if length_penalty is None else length_penalty)
         if W < 1:
@@ -934,16 +958,17 @@ class TransformerDecoderModel(nn.Module):
         dec = self.model.decoder
         if decode_mask is not None:
             return self._decode_kept(ep, B, K, dec, obj_flat, memory.reshape(B * K, -1) if memory.shape[0] != B * K else None,
-                                     decode_mask, decode_capacity, W, alpha, beam, S, tau, topk, sample_seed, top_p)
+                                     decode_mask, decode_capacity, W, alpha, beam, S, tau, topk, sample_seed, top_p, cons)
         if memory.shape[0] != B * K:  # encoder ran once per scene: the indicator adds that proposal's memory row
             indicator = obj_flat.unsqueeze(1) + memory.reshape(B * K, -1).unsqueeze(1)
         else:
             indicator = obj_flat.unsqueeze(1)
-        return self._decode_rows(ep, B, K, dec, indicator, W, alpha, beam, S, tau, topk, sample_seed, top_p)
+        return self._decode_rows(ep, B, K, dec, indicator, W, alpha, beam, S, tau, topk, sample_seed, top_p, cons)
 
-    def _decode_rows(self, ep, B, K, dec, indicator, W, alpha, beam, S, tau, topk, sample_seed, top_p):
+    def _decode_rows(self, ep, B, K, dec, indicator, W, alpha, beam, S, tau, topk, sample_seed, top_p, cons=None):
         """The cached decoding of ``forward_eval`` over the B K rows of ``indicator`` (B K, 1, d): sampled, beam or greedy, fused
-        or through the cached per-operator decoder; the outputs go to ``ep`` as (B, K, ...)."""
+        or through the cached per-operator decoder; the outputs go to ``ep`` as (B, K, ...).  ``cons``: an active
+        ``DecodeConstraints`` or None."""
         caches = [dict() for _ in dec.layers]
         ys = torch.full((B * K, 1), self.word_to_idx["sos"], dtype=torch.long, device=indicator.device)
         embed, pos = self.model.tgt_embed[0], self.model.tgt_embed[1]
@@ -955,30 +980,36 @@ class TransformerDecoderModel(nn.Module):
             if fused and not self.sample_generic:
                 # the greedy loop below at B K S rows with a drawn word in place of the arg-max (caption_decode.sample_decode)
                 got = cd.sample_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), sos, eos, MAX_DES_LEN + 1,
-                                       S, tau, topk, sample_seed, top_p)
+                                       S, tau, topk, sample_seed, top_p, constraints=cons)
                 if got is not None:       # (None: a nucleus over more words than the fused entry takes)
                     self.last_sample_trace = None
                     return self._sample_outputs(ep, B, K, *got)
-            return self._sample_generic(ep, B, K, S, tau, topk, sample_seed, dec, indicator, top_p)
+            return self._sample_generic(ep, B, K, S, tau, topk, sample_seed, dec, indicator, top_p, cons)
         if beam and fused and not self.beam_generic:
             # the greedy loop below at B K W rows: top-W log-probabilities, one selection per sequence, attention through an
             # ancestor table (caption_decode.beam_decode, csrc/caption_decode.hip)
             self.last_beam_trace = {}       # parent int8 / word int32 (n_words, R, W): the selections, for parity tests
             got = cd.beam_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), self.word_to_idx["sos"],
                                  self.word_to_idx["eos"], MAX_DES_LEN + 1, W, alpha, return_all=self.beam_return_all,
-                                 trace=self.last_beam_trace)
+                                 trace=self.last_beam_trace, constraints=cons)
             return self._beam_outputs(ep, B, K, *got)
         if beam:
-            return self._beam_generic(ep, B, K, W, alpha, dec, indicator)
+            return self._beam_generic(ep, B, K, W, alpha, dec, indicator, cons)
         if fused:
             # pre-allocated key / value caches, one token per sequence and step, four launches per layer (caption_decode.greedy_decode)
+            more = {} if cons is None else dict(eos=self.word_to_idx["eos"], constraints=cons)    # (off: today's call, as it stands)
             words = cd.greedy_decode(dec, self.model.generator, embed, pos.pe, indicator.squeeze(1), self.word_to_idx["sos"],
-                                     MAX_DES_LEN + 1)
+                                     MAX_DES_LEN + 1, **more)
             ep["lang_cap"] = words.view(B, K, -1)
             return ep
         words = ys[:, 0]
         for step in range(MAX_DES_LEN + 1):
-            words = self.model.generator(self._cached_step(dec, caches, indicator, step, words)).argmax(dim=-1)
+            out = self._cached_step(dec, caches, indicator, step, words)
+            if cons is None:
+                words = self.model.generator(out).argmax(dim=-1)
+            else:       # the arg-max of the constrained logits over the row's own words so far (ys without sos)
+                from .decode_constraints import apply
+                words = apply(cons, self.model.generator.proj(out), ys[:, 1:], step, self.word_to_idx["eos"]).argmax(dim=-1)
             ys = torch.cat([ys, words.unsqueeze(1)], dim=1)
         ep["lang_cap"] = ys[:, 1:].view(B, K, -1)
         return ep
@@ -1001,7 +1032,8 @@ class TransformerDecoderModel(nn.Module):
             raise RuntimeError("forward_eval: decode_mask: CPU not supported")
         return mask, capacity
 
-    def _decode_kept(self, ep, B, K, dec, obj_flat, memory_flat, mask, capacity, W, alpha, beam, S, tau, topk, sample_seed, top_p):
+    def _decode_kept(self, ep, B, K, dec, obj_flat, memory_flat, mask, capacity, W, alpha, beam, S, tau, topk, sample_seed, top_p,
+                     cons=None):
         """``forward_eval`` under a ``decode_mask``: pack the flagged proposals (``decode_select.select``),
         form the indicator of the packed rows only (``gather``: obj + memory without the B K-row sum), run ``_decode_rows`` on
         them as one scene of that many proposals, and scatter what it returned back to (B, K, ...)."""
@@ -1017,7 +1049,7 @@ class TransformerDecoderModel(nn.Module):
         got = {}
         if kept > 0:
             self._decode_rows(got, 1, kept, dec, ds.gather(obj_flat, memory_flat, rows).unsqueeze(1), W, alpha, beam, S, tau, topk,
-                              sample_seed, top_p)
+                              sample_seed, top_p, cons)
         else:   # nothing to decode: one row of the right shapes that no slot points at
             z = lambda *shape, dtype=torch.float32: torch.zeros(1, 1, *shape, dtype=dtype, device=dev)  # noqa: E731
             got["lang_cap"] = z(L, dtype=torch.long)
@@ -1079,7 +1111,7 @@ class TransformerDecoderModel(nn.Module):
         ep["lang_cap_sample_lengths"] = length.view(B, K, -1)
         return ep
 
-    def _sample_generic(self, ep, B, K, S, tau, topk, seed, dec, indicator, top_p=None):
+    def _sample_generic(self, ep, B, K, S, tau, topk, seed, dec, indicator, top_p=None, cons=None):
         """Sampled decoding through the cached per-operator decoder (``decode_incremental``): everything the fused path does not
         take -- late guide, other head counts, the CPU oracle backend.  Row r S + s is sample s of sequence r."""
         from .sampling import sample
@@ -1096,11 +1128,11 @@ class TransformerDecoderModel(nn.Module):
             return self.model.generator.proj(self._cached_step(dec, caches, ind, i, words))
 
         got = sample(step_fn, R, S, MAX_DES_LEN + 1, self.word_to_idx["sos"], self.word_to_idx["eos"], tau, topk, seed, seed_dev,
-                     device=indicator.device, top_p=top_p)
+                     device=indicator.device, top_p=top_p, constraints=cons)
         self.last_sample_trace = {"gap": got["gap"]}     # (n_words, R S): for parity tests
         return self._sample_outputs(ep, B, K, got["ys"], got["score"], got["length"])
 
-    def _beam_generic(self, ep, B, K, W, alpha, dec, indicator):
+    def _beam_generic(self, ep, B, K, W, alpha, dec, indicator, cons=None):
         """Beam search through the cached per-operator decoder (``decode_incremental``): everything the fused path does not
         take -- late guide, other head counts, the CPU oracle backend.  Row r W + w is hypothesis w of sequence r; a selection
         reorders the key / value caches with ``index_select``."""
@@ -1109,11 +1141,13 @@ class TransformerDecoderModel(nn.Module):
         ind = indicator.repeat_interleave(W, 0)
         caches = [dict() for _ in dec.layers]
 
+        gen = self.model.generator if cons is None else self.model.generator.proj    # (constraints are a rule on the logits)
+
         def step_fn(s, words, parents):
-            return self.model.generator(self._cached_step(dec, caches, ind, s, words, parents))
+            return gen(self._cached_step(dec, caches, ind, s, words, parents))
 
         got = beam_search(step_fn, R, W, MAX_DES_LEN + 1, self.word_to_idx["sos"], self.word_to_idx["eos"], alpha,
-                          device=indicator.device)
+                          device=indicator.device, constraints=cons)
         self.last_beam_trace = {k: got[k] for k in ("parent", "word", "gap")}   # (n_words, R, W) twice, (n_words, R): for parity tests
         if self.beam_return_all:
             return self._beam_outputs(ep, B, K, got["ys"], got["score"], got["beams"], got["scores"], got["lengths"].to(torch.int32))
